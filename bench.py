@@ -14,7 +14,10 @@ per GPU (weak scaling: per-GPU work is fixed as N grows).
 `--gpus N` with N > 1 and no launcher environment starts the N ranks itself (a child `python -m torch.distributed.run`, started before
 this process touches the GPU) and relays rank 0's line; a box with fewer than N GPUs is an error, never a silent 1-GPU run.
 
-Rank 0 prints ONE JSON line (contract in the task description) including
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step) and the run's configuration.  A
+plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  `--dump-outputs DIR` then writes what the
+last timed step computed (fused image, loss values, gradient norm and the updated parameters; inference: the fused image) as
+DIR/<name>.npy in float32, at most 64 MB (dump_outputs).  `--full` adds
   roofline     -- the dominant kernel timed live with HIP events inside the timed region
   parity_path  -- the same step on the parity-grade path (fp32 tensors, 3x3 / 1x1 layers on the matrix pipe as split-operand products,
                   csrc/conv_x3.hip) timed the same way, with its error against the CPU oracle on a small sample (N = 1 only)
@@ -70,12 +73,46 @@ def settle_gc():
     gc.freeze()
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` (name -> tensor) as out_dir/<name>.npy: float64 tensors as float64, everything else as float32.  The files hold at
+    most DUMP_LIMIT_BYTES in all: the arrays are written smallest first, and one that does not fit in what is left is replaced by a fixed
+    sample of its flattened elements (sorted indices drawn by numpy's default_rng(DUMP_SAMPLE_SEED)), the same from run to run for the
+    same shape.  Returns name -> shape written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[k] = (v if v.dtype == torch.float64 else v.float()).cpu().numpy()
+    room = DUMP_LIMIT_BYTES - 256 * len(host)     # (each .npy header is at most a few hundred bytes)
+    written = {}
+    for k in sorted(host, key=lambda k: (host[k].nbytes, k)):
+        a = host[k]
+        if a.nbytes > room:
+            keep = max(0, room // a.itemsize)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        room -= a.nbytes
+        written[k] = list(a.shape)
+    return written
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: 0.4 s of timed steps after 0.1 s of warm-up (30 / 5 measured 1 % lower on the same box: the clocks are still settling)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / per-kernel HIP events inside the timed region, the parity-grade "
+                         "fp32 leg, other_configs and the CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--batch", type=int, default=32, help="image pairs per GPU")
     ap.add_argument("--size", type=int, default=256, help="image height (and width unless --width)")
     ap.add_argument("--width", type=int, default=0)
@@ -488,13 +525,19 @@ def main():
     img1 = torch.rand(B * world, 1, S, Wd, generator=gen)[rank * B:(rank + 1) * B].to(dev)  # synthetic IR / visible pairs in [0,1)
     img2 = torch.rand(B * world, 1, S, Wd, generator=gen)[rank * B:(rank + 1) * B].to(dev)
 
-    def infer_step():
-        with torch.no_grad():
-            return model(img1, img2).mean()
+    dump = args.dump_outputs is not None
+    last = {}     # keep=True: what the step computed, for --dump-outputs (only the last timed step keeps it)
 
-    def step():
+    def infer_step(keep=False):
+        with torch.no_grad():
+            f = model(img1, img2)
+            if keep:
+                last["fused_image"] = f
+            return f.mean()
+
+    def step(keep=False):
         if args.mode == "infer":
-            return infer_step()
+            return infer_step(keep)
         opt.zero_grad(set_to_none=True)
         f = model(img1, img2)
         if l_all is not None:
@@ -507,6 +550,8 @@ def main():
         opt.stage_scalars(vals)      # (data parallel) the loss values ride in the early gradient all-reduce
         tot.backward(unit_gradient(tot))   # (= tot.backward(); core/loss.py: a cached ones tensor, as train.py does)
         opt.step(scalars=vals)
+        if keep:
+            last.update(fused_image=f, losses=torch.stack([v.reshape(()) for v in vals]) if isinstance(vals, list) else vals)
         return tot
 
     for _ in range(args.warmup):
@@ -523,28 +568,37 @@ def main():
             return a + b + c, a, b, c
         gstep = GraphedStep(model, losses, opt, img1, img2)
 
-        def step():   # noqa: F811
-            return gstep(img1, img2)[0]
+        def step(keep=False):   # noqa: F811
+            outs = gstep(img1, img2)
+            if keep:
+                last.update(fused_image=gstep.imgf, losses=torch.stack([v.reshape(()) for v in outs]))
+            return outs[0]
         for _ in range(2):
             step()
-    hbm_tag = args.hbm_tag
-    enc_stream = args.dtype == "bf16" and os.environ.get("MMIF_ENC_STREAM", "1") != "0" and args.model in ("PFNetv1", "DenseFuse", "PFNetv2", "VIFNet")
-    if hbm_tag == "auto":   # the encoder: ONE streaming launch for its 2 x 4 layers, or (layer-wise) its widest thin layer 48 -> 16
-        hbm_tag = "encode:fwd" if enc_stream else ({"PFNetv1": "encode1.1.2:fwd", "DenseFuse": "encode.1.2:fwd", "PFNetv2": "encode.1.2:fwd", "VIFNet": "encode.1.2:fwd"}.get(args.model, "") if args.mode == "train" else "")
-    tags = {f"{args.roofline_layer}:{k}" for k in ("fwd", "dgrad", "wgrad")} | ({hbm_tag} if hbm_tag else set())
-    if hbm_tag == "encode:fwd" and args.mode == "train":
-        tags |= {"encode:bwd"}      # the fused encoder backward (csrc/enc_bwd.hip), when the engine takes it
-    every = args.roofline_every if args.roofline_every > 0 else max(1, args.steps // 5)
-    # the sampled steps' events exist before the clock starts (created and recorded once), and one untimed step runs the sampled form of the
-    # backward (wgrad and dgrad of the wide layers as two calls): nothing is created or first-used inside the timed region
-    T.prealloc_events(tags, (args.steps + every - 1) // every + 2)
-    T.PROFILE_TAGS = tags
-    step()
-    T.PROFILE_TAGS = set()
-    for evs in T.PROFILE_EVENTS.values():     # (the untimed sampled step's events go back to the pool)
-        for pair in evs:
-            T.PROFILE_EVENT_POOL.setdefault("_spare", []).append(pair)
-    T.PROFILE_EVENTS.clear()
+    if args.full:
+        hbm_tag = args.hbm_tag
+        enc_stream = args.dtype == "bf16" and os.environ.get("MMIF_ENC_STREAM", "1") != "0" and args.model in ("PFNetv1", "DenseFuse", "PFNetv2", "VIFNet")
+        if hbm_tag == "auto":   # the encoder: ONE streaming launch for its 2 x 4 layers, or (layer-wise) its widest thin layer 48 -> 16
+            hbm_tag = "encode:fwd" if enc_stream else ({"PFNetv1": "encode1.1.2:fwd", "DenseFuse": "encode.1.2:fwd", "PFNetv2": "encode.1.2:fwd", "VIFNet": "encode.1.2:fwd"}.get(args.model, "") if args.mode == "train" else "")
+        tags = {f"{args.roofline_layer}:{k}" for k in ("fwd", "dgrad", "wgrad")} | ({hbm_tag} if hbm_tag else set())
+        if hbm_tag == "encode:fwd" and args.mode == "train":
+            tags |= {"encode:bwd"}      # the fused encoder backward (csrc/enc_bwd.hip), when the engine takes it
+        every = args.roofline_every if args.roofline_every > 0 else max(1, args.steps // 5)
+        # the sampled steps' events exist before the clock starts (created and recorded once), and one untimed step runs the sampled form of the
+        # backward (wgrad and dgrad of the wide layers as two calls): nothing is created or first-used inside the timed region
+        T.prealloc_events(tags, (args.steps + every - 1) // every + 2)
+        T.PROFILE_TAGS = tags
+        step()
+        T.PROFILE_TAGS = set()
+        for evs in T.PROFILE_EVENTS.values():     # (the untimed sampled step's events go back to the pool)
+            for pair in evs:
+                T.PROFILE_EVENT_POOL.setdefault("_spare", []).append(pair)
+        T.PROFILE_EVENTS.clear()
+    else:
+        # no HIP events anywhere: the timed steps are the plain step.  The full run's untimed sampled step still runs (plain), so that both
+        # take warmup + 1 + steps train steps and end on the same model state and final_loss
+        hbm_tag, tags, every = "", set(), 1
+        step()
     settle_gc()
     if use_dist:
         dist.barrier()
@@ -562,7 +616,7 @@ def main():
         if diag and i % 10 == 0:
             dev_ev[i // 10].record()
         T.PROFILE_TAGS = tags if i % every == 0 else set()   # (live, inside the timed region -- on a sample of its steps)
-        tot = step()
+        tot = step(dump and i == args.steps - 1)
         if diag:
             hts.append(time.perf_counter())
     if use_dist:
@@ -580,6 +634,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     loss = float(tot.item())
+    if rank == 0 and dump:
+        if args.mode == "train":
+            last["grad_norm"] = opt.grad_norm
+            last.update({f"param.{k}": p for k, p in model.named_parameters()})
+        dump_outputs(args.dump_outputs, last)
+        last.clear()
 
     if rank == 0:
         pairs = B * world * args.steps
@@ -587,7 +647,7 @@ def main():
         workload_id = f"{args.model} {args.mode} B={B} {Wd}x{S} {args.dtype}"
         # the wide layer's three launches, timed live (HIP events on the launch stream, inside the timed region); `roofline` is the one
         # with the largest share of the step
-        roofs = conv_rooflines(T, model._engine, args.roofline_layer, B, S, Wd, args.dtype, dt / args.steps * 1e3, workload_id) if getattr(model, "_engine", None) is not None else {}
+        roofs = conv_rooflines(T, model._engine, args.roofline_layer, B, S, Wd, args.dtype, dt / args.steps * 1e3, workload_id) if args.full and getattr(model, "_engine", None) is not None else {}
         roof = max(roofs.values(), key=lambda r: r["step_share"]) if roofs else None
         roof_hbm = None
         evh = T.PROFILE_EVENTS.get(hbm_tag, []) if hbm_tag else []
@@ -636,7 +696,7 @@ def main():
         ideal = ideal_pairs_per_s(args.model, S, Wd, args.dtype, 3 if args.dtype == "fp32" else 1) if args.mode == "train" else None
         out = {
             "metric": "image-pairs/sec at 256x256, PFNet train step" if args.mode == "train" else f"image-pairs/sec at {Wd}x{S}, {args.model} inference", "value": value, "unit": "image-pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "graph": bool(args.graph and args.mode == "train"),
             "config": {"workload": (f"{args.model} train step (fwd + SSIM/pixel/grad losses + bwd + clip + Adam)" if args.mode == "train" else f"{args.model} forward (no_grad, test.py path)") + f", {Wd}x{S} synthetic IR/visible pairs, "
@@ -651,7 +711,7 @@ def main():
             "roofline": roof,
             "roofline_kernels": roofs or None,
             "roofline_sampling": {"every_nth_timed_step": every, "timed_steps": args.steps,
-                                  "note": "HIP events around the named launches, recorded inside the timed region on every n-th step"},
+                                  "note": "HIP events around the named launches, recorded inside the timed region on every n-th step"} if args.full else None,
             "roofline_hbm": roof_hbm,
             "roofline_hbm_bwd": roof_hbm_bwd,
             "parity_path": None,
@@ -659,13 +719,13 @@ def main():
             "cpu_baseline": None,
         }
         assert out["n_gpus"] == args.gpus
-        if world == 1 and not args.no_parity_path and args.mode == "train" and args.dtype == "bf16" and args.model in ("PFNetv1", "DenseFuse", "PFNetv2", "VIFNet"):
+        if args.full and world == 1 and not args.no_parity_path and args.mode == "train" and args.dtype == "bf16" and args.model in ("PFNetv1", "DenseFuse", "PFNetv2", "VIFNet"):
             out["parity_path"] = parity_leg(args, dev, img1, img2)
         headline = (args.model, args.mode, args.dtype, B, S, Wd) == ("PFNetv1", "train", "bf16", 32, 256, 256)
-        if world == 1 and not args.no_other_configs and headline and not args.graph:
+        if args.full and world == 1 and not args.no_other_configs and headline and not args.graph:
             del tot
             out["other_configs"] = other_configs_leg(args, dev)
-        if world == 1 and not args.no_cpu_baseline and args.mode == "train" and Wd == S:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "train" and Wd == S:
             out["cpu_baseline"] = cpu_baseline(args.model, S, args.cpu_sample)
     else:
         out = None

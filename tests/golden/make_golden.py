@@ -13,7 +13,7 @@ GPU box.  Fixture map:
 
   f1_loss_known_answer.json  core/loss.py:388-423 recipe (seed 0, rand(2,1,256,256) x3)
   f2_loss_grads.npz          loss values + d/dimgf on closed-form images (incl. clamp / tie cases)
-  f3_conv.npz                ConvLayer fwd + (dx, dW, db) per (Cin, Cout, k)
+  f3_conv.npz, f3_conv_2.npz ConvLayer fwd + (dx, dW, db) per (Cin, Cout, k) (the cases split in two halves)
   f4_blocks.npz              DenseBlock / ConvBlock / RFN / NestDecoder / fusion fns fwd + bwd
   f5_models.npz              PFNetv1, PFNetv2, DenseFuse, NestFuse, RFNNest forward + grad digests
   f5_manifest.json           state_dict key/shape manifests
@@ -30,6 +30,8 @@ GPU box.  Fixture map:
   f7_metric_ssim.json        core/metric.py:316-364 calc_ssim (the SSIM that test.py:49-52 reports) on closed-form images
   f16_stock_fallbacks.npz    the argument combinations that run as stock torch ops (core/_stock.py): SSIMLoss(use_padding=True) in its four
                              modes, SSIM(size_average=False) / other windows, metric calc_ssim(win 7, padding, full), channel_pooling('nuclear')
+  f17_reference_init.json    PFNetv1's state_dict after torch.manual_seed(0): key, shape, dtype, sha256 of the bytes
+  f18_sample_folders.json    data/samples layout: relative path, width, height, PIL mode, format of every image
 """
 import json
 import os
@@ -194,7 +196,10 @@ def make_f3():
         out[name + "_dx"] = x.grad.numpy()
         out[name + "_dw"] = layer.layers[0].weight.grad.numpy()
         out[name + "_db"] = layer.layers[0].bias.grad.numpy()
-    save("f3_conv.npz", out)
+    # two files, the first half of the cases and the rest, to keep each fixture under 1 MiB
+    first = {c[0] for c in F3_CASES[:(len(F3_CASES) + 1) // 2]}
+    save("f3_conv.npz", {k: v for k, v in out.items() if k.rsplit("_", 1)[0] in first})
+    save("f3_conv_2.npz", {k: v for k, v in out.items() if k.rsplit("_", 1)[0] not in first})
 
 
 # ---------------------------------------------------------------- F11 (row n4: the general ConvLayer forms)
@@ -629,8 +634,33 @@ def make_f16():
     save("f16_stock_fallbacks.npz", out)
 
 
+def make_f17():
+    """The reference's PFNetv1 initialisation after torch.manual_seed(0) (core/block.py init): per state_dict entry its shape and the
+    sha256 of its float32 bytes, so that a test can check the mirror's init bit for bit without the reference."""
+    import hashlib
+    torch.manual_seed(0)
+    sd = rmodel.PFNetv1().state_dict()
+    out = {"model": "PFNetv1", "seed": 0, "torch": torch.__version__,
+           "tensors": [[k, list(v.shape), str(v.dtype), hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest()] for k, v in sd.items()]}
+    json.dump(out, open(os.path.join(HERE, "f17_reference_init.json"), "w"), indent=0)
+
+
+def make_f18():
+    """The layout of the reference's demo sample folders (data/samples: relative path, width, height, PIL mode, format of every image), so
+    that a test can rebuild a stand-in tree of the same names, sizes and colour modes."""
+    from PIL import Image
+    base = os.path.join(REF, "data", "samples")
+    files = []
+    for dirpath, _, names in sorted(os.walk(base)):
+        for n in sorted(names):
+            p = os.path.join(dirpath, n)
+            with Image.open(p) as im:
+                files.append([os.path.relpath(p, base).replace(os.sep, "/"), im.size[0], im.size[1], im.mode, im.format])
+    json.dump({"files": files}, open(os.path.join(HERE, "f18_sample_folders.json"), "w"), indent=0)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f14", "f15", "f16"]
+    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f14", "f15", "f16", "f17", "f18"]
     for w in which:
         globals()["make_" + w]()
         print("wrote", w)

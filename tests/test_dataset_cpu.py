@@ -8,7 +8,7 @@ import pytest
 import torch
 from PIL import Image
 
-REF_SAMPLES = "/root/reference/data/samples"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _img(h, w, seed, rgb=False):
@@ -109,17 +109,28 @@ def test_entry_points_build_the_dataset_like_the_reference(tmp_path):
     assert "WarmupLR(optimizer, 0.001, len(train_loader))" in tr and "log_dir, logger = make_logger(BASE_DIR)" in tr
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SAMPLES), reason="reference samples not present (GPU box)")
-def test_reference_sample_folders_load():
+def sample_folders(root):
+    """A stand-in for the reference's demo sample folders (data/samples) with the same file names, sizes, colour modes and formats
+    (golden F18); the pixels are a fixed pattern."""
+    import json
+    for rel, w, h, mode, fmt in json.load(open(os.path.join(GOLDEN, "f18_sample_folders.json")))["files"]:
+        path = os.path.join(root, *rel.split("/"))
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        Image.fromarray(_img(h, w, len(rel), rgb=mode == "RGB"), mode).save(path, fmt)
+    return root
+
+
+def test_reference_sample_folders_load(tmp_path):
     """the reference's own sample folders (data/dataset.py:208-216 demo): 16 infrared pairs (colour vis files), 5 polar pairs"""
     from data.dataset import FusionDataset
-    ir = FusionDataset(os.path.join(REF_SAMPLES, "infrared"), set_name="test", set_type="test", img_type="ir", norm="min-max",
+    samples = sample_folders(str(tmp_path / "samples"))
+    ir = FusionDataset(os.path.join(samples, "infrared"), set_name="test", set_type="test", img_type="ir", norm="min-max",
                        transform=True, fix_size=True)
     assert len(ir) == 16
     a, b = ir[0]
     assert a.shape == b.shape == (1, 256, 256)
-    po = FusionDataset(os.path.join(REF_SAMPLES, "polar"), set_name="test", set_type="test", img_type="po")
+    po = FusionDataset(os.path.join(samples, "polar"), set_name="test", set_type="test", img_type="po")
     assert len(po) == 5 and po[0][0].shape == (1, 1024, 1224)
     from data.patches import FusionPatches
-    pp = FusionPatches(os.path.join(REF_SAMPLES, "polar"), set_name="test", set_type="test", img_type="po")
+    pp = FusionPatches(os.path.join(samples, "polar"), set_name="test", set_type="test", img_type="po")
     assert len(pp) == 5 * (1024 // 64) * (1224 // 64)

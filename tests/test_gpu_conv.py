@@ -32,7 +32,7 @@ def _run_layer(case):
 @pytest.mark.parametrize("case", F3_CASES, ids=[c[0] for c in F3_CASES])
 def test_conv_fp32_vs_golden(case):
     """fp32 storage, VALU kernels: the north-star parity bar is 1e-3 relative; we hold 1e-4."""
-    ref = np.load(os.path.join(G, "f3_conv.npz"))
+    ref = {**np.load(os.path.join(G, "f3_conv.npz")), **np.load(os.path.join(G, "f3_conv_2.npz"))}
     name = case[0]
     with dtype_ctx("fp32"):
         y, dx, dw, db = _run_layer(case)

@@ -82,7 +82,7 @@ def test_bench_two_ranks_gloo_one_device():
     the LAST thing on stdout (the other ranks' stdout goes to stderr)."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--one-device", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-parity-path"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-parity-path"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, f"bench.py --gpus 2 failed:\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     out = json.loads(lines[-1])
@@ -136,7 +136,7 @@ def test_bench_other_configs_block_small_shapes(monkeypatch):
 
 def test_bench_single_gpu_line_has_the_contract_fields():
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "4", "--size", "64", "--cpu-sample", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--batch", "4", "--size", "64", "--cpu-sample", "2",
                         "--parity-steps", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, f"bench.py failed:\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -152,3 +152,27 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     assert pp["rel_err_vs_oracle"] < 1e-3 and pp["grad_rel_err_vs_oracle"] < 1e-3 and len(pp["oracle_samples"]) == 2
     assert pp["roofline"]["peak"] == 2500.0 and pp["roofline"]["products_per_tap"] == 3 and pp["roofline"]["frac"] < 1.0
     assert abs(pp["roofline"]["executed_mfma_tflops"] - 3 * pp["roofline"]["algorithmic_fp32_tflops"]) < 1e-6 * pp["roofline"]["executed_mfma_tflops"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and measures nothing beyond the headline: no HIP events, no parity
+    leg, no other configs, no CPU baseline.  --dump-outputs writes the last timed step's fused image, loss values, gradient norm and
+    updated parameters as float32 .npy files; the dumped total loss is the line's final_loss."""
+    import json
+    out_dir = tmp_path / "outs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "64",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, f"bench.py failed:\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["full"] is False and out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 2 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    for k in ("roofline", "roofline_kernels", "roofline_sampling", "roofline_hbm", "roofline_hbm_bwd", "parity_path", "other_configs", "cpu_baseline"):
+        assert out[k] is None, k
+    files = {p.name: np.load(p) for p in out_dir.iterdir()}
+    assert files["fused_image.npy"].shape == (2, 1, 64, 64) and files["losses.npy"].shape == (4,) and files["grad_norm.npy"].shape == (1,)
+    assert sum(1 for n in files if n.startswith("param.")) == 26
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert abs(float(files["losses.npy"][0]) - out["final_loss"]) <= 1e-6 * abs(out["final_loss"])
+    assert sum(p.stat().st_size for p in out_dir.iterdir()) <= 64 * 10**6

@@ -116,30 +116,19 @@ def test_state_dict_manifest_and_init(name):
 
 
 def test_reference_init_is_bitwise_reproduced_when_reference_is_present():
-    ref_root = "/root/reference"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference not mounted (GPU box)")
-    import importlib.util
-    import sys
+    """The mirror's PFNetv1 init after torch.manual_seed(0) is the reference's bit for bit: same keys in the same order, same shapes and
+    dtypes, and the sha256 of every tensor's bytes equal to the reference's (golden F17, recorded by tests/golden/make_golden.py)."""
+    import hashlib
     import core.model as M
+    ref = json.load(open(os.path.join(G, "f17_reference_init.json")))
+    assert ref["model"] == "PFNetv1" and ref["seed"] == 0
     torch.manual_seed(0)
     mine = M.PFNetv1().state_dict()
-    # import the reference's core package under a private name
-    saved = {k: sys.modules.pop(k) for k in list(sys.modules) if k == "core" or k.startswith("core.")}
-    sys.path.insert(0, ref_root)
-    try:
-        sys.dont_write_bytecode = True
-        import core.model as R
-        torch.manual_seed(0)
-        ref = R.PFNetv1().state_dict()
-    finally:
-        sys.path.remove(ref_root)
-        for k in [k for k in sys.modules if k == "core" or k.startswith("core.")]:
-            sys.modules.pop(k)
-        sys.modules.update(saved)
-    assert list(mine) == list(ref)
-    for k in ref:
-        assert torch.equal(mine[k], ref[k]), k
+    assert list(mine) == [k for k, _, _, _ in ref["tensors"]]
+    for k, shape, dtype, digest in ref["tensors"]:
+        v = mine[k]
+        assert list(v.shape) == shape and str(v.dtype) == dtype, k
+        assert hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest() == digest, k
 
 
 def test_conv_layer_signature_and_fallback_rules():
@@ -287,3 +276,29 @@ def test_bench_self_launch_refuses_a_smaller_box(monkeypatch):
     assert 1024 < p1 < 65536 and 1024 < p2 < 65536
     # SURVEY 8(d)'s ideal for the headline config: 1 / max(42.8 us, 45.8 us) = 21.8 k pairs/s
     assert abs(bench.ideal_pairs_per_s("PFNetv1", 256, 256, "bf16") - 21850) < 100
+
+
+def test_bench_dump_outputs_budget_dtypes_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py's --dump-outputs writer: float32 files (float64 stays float64), at most 64 MB in all, and an array too large for what is
+    left replaced by the same seeded sample of its elements on every call.  A plain run is the default; --full is opt-in."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    args = bench.parse()
+    assert args.steps == 7 and args.full is False and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+    big = torch.arange(17_000_000, dtype=torch.float32)
+    arrays = {"big": big, "half": torch.full((5,), 1.5, dtype=torch.bfloat16), "dbl": torch.arange(3, dtype=torch.float64)}
+    shapes = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert shapes[0] == shapes[1] and shapes[0]["half"] == [5] and shapes[0]["dbl"] == [3] and 0 < shapes[0]["big"][0] < big.numel()
+    for d in ("a", "b"):
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_LIMIT_BYTES == 64 * 10**6
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b) and np.all(np.diff(a) >= 0)     # the same sorted sample both times
+    assert np.load(tmp_path / "a" / "half.npy").dtype == np.float32 and np.load(tmp_path / "a" / "dbl.npy").dtype == np.float64
+    small = bench.dump_outputs(str(tmp_path / "c"), {"x": torch.arange(6.0).reshape(2, 3)})
+    assert small == {"x": [2, 3]} and np.array_equal(np.load(tmp_path / "c" / "x.npy"), np.arange(6.0, dtype=np.float32).reshape(2, 3))

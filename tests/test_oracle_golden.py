@@ -135,7 +135,7 @@ def f3_tensors(case):
 
 @pytest.mark.parametrize("case", F3_CASES, ids=[c[0] for c in F3_CASES])
 def test_f3_conv_layer(case):
-    ref = np.load(os.path.join(G, "f3_conv.npz"))
+    ref = {**np.load(os.path.join(G, "f3_conv.npz")), **np.load(os.path.join(G, "f3_conv_2.npz"))}
     name, relu = case[0], case[4]
     x, w, b, gy = f3_tensors(case)
     y = O.conv2d_reflect_fwd(x, w, b, relu)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """profiles/<tag>_traffic.json from the two TCC counter passes of tools/prof_pmc.sh (run on the GPU box, repo root):
-    tools/make_traffic.py <tag> > gpurun_out/traffic_<tag>.json
+    tools/make_traffic.py <tag> > $OUT/traffic_<tag>.json   ($OUT: the profiling scripts' output folder, default prof_out)
 HBM bytes per launch of the roofline kernels of the default bench (PFNetv1 train B=32 256x256 bf16): decode.0's forward
 (conv_dma_kernel<false, 0>: decode.0 and decode.1 alternate per step; decode.0 is the launch with the larger WRITE_SIZE), its dgrad and
 weight gradient (conv_dma_kernel<true, 2> / wgrad_dma_kernel: decode.0 is the launch with the larger FETCH_SIZE) and the streaming
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def per_dispatch(counter, sub):
-    path = glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}_{counter}", "**", "*counter_collection.csv"), recursive=True)[0]
+    path = glob.glob(os.path.join(ROOT, os.environ.get("OUT", "prof_out"), f"pmc_{tag}_{counter}", "**", "*counter_collection.csv"), recursive=True)[0]
     vals = defaultdict(float)
     with open(path) as f:
         for r in csv.DictReader(f):
@@ -50,7 +50,7 @@ fe, we = per_dispatch("FETCH_SIZE", "enc_stream2_fwd_kernel"), per_dispatch("WRI
 fb, wb = per_dispatch("FETCH_SIZE", "enc_bwd_fused_kernel"), per_dispatch("WRITE_SIZE", "enc_bwd_fused_kernel")
 B, S = 32, 256
 out = {"workload": "PFNetv1 train B=32 256x256 bf16", "lib_sha256": h,
-       "command": f"tools/prof_pmc.sh {tag}: rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, separately, WRITE_SIZE) --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity-path",
+       "command": f"tools/prof_pmc.sh {tag}: rocprofv3 --kernel-trace --pmc FETCH_SIZE (and, separately, WRITE_SIZE) --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-parity-path",
        "kernels": {
            "decode.0:fwd": entry("conv_dma_kernel<false, 0> 128->128 k3 (decode.0 forward)", f0, w0, float(B) * S * S * 256 * 2),
            "encode:fwd": entry("enc_stream2_fwd_kernel<2>, both encoder branches", fe, we, float(B) * S * S * 2 * (4 + 64 * 2),

@@ -1,12 +1,13 @@
 #!/bin/bash
+export OUT=${OUT:-prof_out}; mkdir -p "$OUT"   # output folder of this script and the ones it calls
 # All of a round's profile evidence for the default bench in one go (run on the GPU box from the repo root):  tools/prof_round.sh r03
 #   kernel stats (bf16 default + fp32 parity path), per-dispatch durations of the two decode convs, SQ counters, TCC traffic passes,
-#   traffic json stamped with the library build.  Copy gpurun_out/<tag>_* into profiles/ afterwards.
+#   traffic json stamped with the library build.  Copy $OUT/<tag>_* into profiles/ afterwards.
 tag=$1
 tools/prof_bench.sh ${tag} --no-parity-path > /dev/null 2>&1
-cp gpurun_out/kstats_${tag}.txt gpurun_out/${tag}_kernel_stats_bench_pfnetv1_b32_256_bf16.txt
-db=$(find gpurun_out/prof_${tag} -name "*.db" | head -1)
-python3 - "$db" > gpurun_out/${tag}_decode_fwd_per_dispatch.txt <<'PY'
+cp $OUT/kstats_${tag}.txt $OUT/${tag}_kernel_stats_bench_pfnetv1_b32_256_bf16.txt
+db=$(find $OUT/prof_${tag} -name "*.db" | head -1)
+python3 - "$db" > $OUT/${tag}_decode_fwd_per_dispatch.txt <<'PY'
 import sqlite3, sys
 con = sqlite3.connect(sys.argv[1])
 rows = con.execute("select name, start, end from kernels order by start").fetchall()
@@ -22,9 +23,9 @@ for pat, nm in (("conv_dma_kernel<true", "dgrad decode.1 / decode.0"), ("wgrad_d
         print(f"{nm} (first launched / second launched per step): mean {sum(a) / len(a):.1f} / {sum(b) / max(1, len(b)):.1f}")
 PY
 tools/prof_bench.sh ${tag}fp32 --dtype fp32 > /dev/null 2>&1
-cp gpurun_out/kstats_${tag}fp32.txt gpurun_out/${tag}_kernel_stats_bench_pfnetv1_b32_256_fp32_x3.txt
+cp $OUT/kstats_${tag}fp32.txt $OUT/${tag}_kernel_stats_bench_pfnetv1_b32_256_fp32_x3.txt
 tools/prof_sq.sh ${tag} > /dev/null 2>&1
-cp gpurun_out/sq_${tag}.txt gpurun_out/${tag}_pmc_sq_bench_pfnetv1_b32_256_bf16.txt
+cp $OUT/sq_${tag}.txt $OUT/${tag}_pmc_sq_bench_pfnetv1_b32_256_bf16.txt
 tools/prof_pmc.sh ${tag} > /dev/null 2>&1
-cp gpurun_out/pmc_${tag}_FETCH_SIZE.txt gpurun_out/${tag}_pmc_tcc_fetch_size.txt
-cp gpurun_out/pmc_${tag}_WRITE_SIZE.txt gpurun_out/${tag}_pmc_tcc_write_size.txt
+cp $OUT/pmc_${tag}_FETCH_SIZE.txt $OUT/${tag}_pmc_tcc_fetch_size.txt
+cp $OUT/pmc_${tag}_WRITE_SIZE.txt $OUT/${tag}_pmc_tcc_write_size.txt
