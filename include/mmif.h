@@ -383,6 +383,40 @@ int mmif_ssim_loss_mode(const float* img1, const float* img2, const float* imgf,
  * mmif_ssim_loss_mode_workspace(n, h, w, 1). */
 int mmif_ssim_terms(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, float data_range,
                     float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- Fusion-quality metrics of eval.py (core/metric.py:1-491): per-SAMPLE raw terms of fp32 [n][h][w] images holding 0..255
+ * values; the per-image and pooled values are finished from them on the host side (core/metric.py of this package).  fp64 block
+ * partials + fixed-order second stages: a sample's terms are bit-identical whatever batch it is in.
+ * moments (:25-100): k = 1..3 images imgs[j] (a HOST array of k device pointers); out[n][k + k*k + 3k] fp64 = the k means, the
+ * k x k centred Gram matrix sum (x_j - mu_j)(x_l - mu_l), per image the AG sum over (h-1)(w-1) pixels, sum dy^2 ((h-1) x w) and
+ * sum dx^2 (h x (w-1)).  h, w >= 2. */
+size_t mmif_metric_moments_workspace(int32_t n, int32_t h, int32_t w, int32_t k);
+int mmif_metric_moments(const float* const* imgs, int32_t k, int32_t n, int32_t h, int32_t w, double* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* hist (:103-166): u32 counts hx[n][256], hy[n][256] of x and y and hxy[n][256][256] of the pairs (x, y) (zeroed here first), as
+ * torch.histc(v, 256, 0, 256) / np.histogram2d: bin floor(v) on [0, 256), 256 -> 255, values outside [0, 256] dropped (a pair if
+ * either is).  Integer atomics only. */
+int mmif_metric_hist(const float* x, const float* y, int32_t n, int32_t h, int32_t w, uint32_t* hx, uint32_t* hy, uint32_t* hxy,
+                     void* stream);
+/* entropy (:119-190): out[n][4] fp64 = EN(x), EN(y), joint entropy, CE(x||y) of the counts of mmif_metric_hist, p = count / numel
+ * (numel counts the dropped values too); only p != 0 (p1 p2 != 0 for CE) terms. */
+int mmif_metric_entropy(const uint32_t* hx, const uint32_t* hy, const uint32_t* hxy, int32_t n, int64_t numel, double* out,
+                        void* stream);
+/* qabf (:192-287, 'qabf' constants): out[n][5] fp64 = sum(Qaf wa + Qbf wb), sum(wa + wb), sum AM((1-Qaf) wa + (1-Qbf) wb),
+ * the same under RR, sum AM (2 - Qaf - Qbf)(wa + wb) with w = g^L, AM = gf > max(ga, gb), RR = gf <= max(ga, gb).  h, w >= 2. */
+size_t mmif_metric_qabf_workspace(int32_t n, int32_t h, int32_t w);
+int mmif_metric_qabf(const float* a, const float* b, const float* f, int32_t n, int32_t h, int32_t w, double L, double* out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* vif (:406-491) of the pairs (a, f) and (b, f): out[4][n][6] fp64 = per scale sum N1, D1, N2, D2, sum (g1 < g2 ? N1 : N2),
+ * sum (g1 < g2 ? D1 : D2).  taps: HOST fp32 array of the four normalised 1-D Gaussians (17, 9, 5, 3 taps = 34 floats, the
+ * reference's create_window); 2-D weight = fp32 product.  Images >= 41x41 (workspace query returns 0 below). */
+size_t mmif_metric_vif_workspace(int32_t n, int32_t h, int32_t w);
+int mmif_metric_vif(const float* a, const float* b, const float* f, int32_t n, int32_t h, int32_t w, const float* taps, double* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* msssim (:368-403) on the SSIM kernels of csrc/loss_modes.hip: out[2][6][n] fp32, pair p = (a, f) | (b, f): cs means of levels 0..3,
+ * ssim mean of level 4, slot 5 = level-0 ssim mean.  b may be NULL (pair 2 = pair 1).  Images >= 161x161. */
+size_t mmif_metric_msssim_workspace(int32_t n, int32_t h, int32_t w);
+int mmif_metric_msssim(const float* a, const float* b, const float* f, int32_t n, int32_t h, int32_t w, float data_range, float* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
 /* TVLoss core/loss.py:347-358 = NormLoss(l1|l2)(x[1:] - x[:-1]) + NormLoss(x[:, 1:] - x[:, :-1]) over n images [h][w]. */
 size_t mmif_tv_loss_workspace(void);
 int mmif_tv_loss(const float* x, int32_t n, int32_t h, int32_t w, float weight, int32_t l2, float* loss_out, float* grad_out,

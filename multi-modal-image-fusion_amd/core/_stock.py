@@ -125,3 +125,20 @@ def nuclear_pooling(tensor):
     c = tensor.shape[1]
     s = torch.linalg.svdvals(tensor[0].clamp(min=eps))      # [C, min(h, w)]
     return s.sum(dim=1).reshape(1, c, 1, 1).to(tensor.device)
+
+
+def metric_msssim(img1, img2, win_size=11, data_range=255.0, use_padding=False):
+    """core.metric.calc_msssim (core/metric.py:368-403) for what the HIP path does not cover (use_padding, win_size != 11, images
+    below 161 px): pooled ssim / cs means of a 2x2 average-pool pyramid, window min(win_size, h, w) with sigma 1.5 on every level"""
+    a, b, vals = img1, img2, []
+    for lvl in range(len(MS_WEIGHTS)):
+        ssim, cs = metric_ssim(a, b, win_size, data_range, use_padding, full=True)
+        if lvl == len(MS_WEIGHTS) - 1:
+            vals.append(ssim)
+            break
+        vals.append(cs)
+        ph, pw = a.shape[-2] % 2, a.shape[-1] % 2
+        a = F.avg_pool2d(F.pad(a, (0, pw, 0, ph), 'reflect'), 2, 2)
+        b = F.avg_pool2d(F.pad(b, (0, pw, 0, ph), 'reflect'), 2, 2)
+    weights = torch.tensor(MS_WEIGHTS, dtype=torch.float32).to(img1)
+    return torch.prod(torch.stack(vals, dim=0).clamp(min=1e-7) ** weights, dim=0)

@@ -553,3 +553,68 @@ extern "C" int mmif_tv_loss(const float* x, int32_t n, int32_t h, int32_t w, flo
     hipLaunchKernelGGL(tv_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, nb, loss_out);
     return check_launch("tv_finish");
 }
+
+// workspace (floats): [partial 4*n*tiles | sums 4n | pyramid: 3 images per level 1..4]
+extern "C" size_t mmif_metric_msssim_workspace(int32_t n, int32_t h, int32_t w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    size_t fl = 4 * (size_t)n * cdiv(h, MT_) * cdiv(w, MT_) + 4 * (size_t)n + 64;
+    size_t hl = h, wl = w;
+    for (int l = 1; l < 5; ++l) {
+        hl = (hl + 1) / 2;
+        wl = (wl + 1) / 2;
+        fl += 3 * (size_t)n * hl * wl + 64;
+    }
+    return fl * sizeof(float);
+}
+
+/* calc_msssim core/metric.py:368-403 (window 11, sigma 1.5, valid; images >= 161x161) of the pairs (a, f) and (b, f) on the loss's
+ * kernels and pyramid: out[p][l][s] = per-sample mean of the cs map on level l = 0..3, of the ssim map on level 4, and slot l = 5 the
+ * level-0 ssim mean (calc_ssim).  b == NULL: pair 2 repeats pair 1. */
+extern "C" int mmif_metric_msssim(const float* a, const float* b, const float* f, int32_t n, int32_t h, int32_t w, float data_range,
+                                  float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    MMIF_REQUIRE(a && f && out && workspace, "metric_msssim: NULL argument");
+    MMIF_REQUIRE(n > 0 && h >= 161 && w >= 161, "metric_msssim: images must be at least 161x161 (11x11 window on level 4); got %dx%d", h, w);
+    if (workspace_bytes < mmif_metric_msssim_workspace(n, h, w)) {
+        set_error("metric_msssim: workspace too small");
+        return MMIF_EWORKSPACE;
+    }
+    if (b == nullptr) b = a;
+    hipStream_t st = (hipStream_t)stream;
+    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
+    float* partial = (float*)workspace;
+    float* sums = partial + 4 * (size_t)n * cdiv(h, MT_) * cdiv(w, MT_);
+    float* pyr = sums + 4 * n + 64;
+    int hs[5], wsz[5];
+    const float* la[5] = {a};
+    const float* lb[5] = {b};
+    const float* lf[5] = {f};
+    hs[0] = h;
+    wsz[0] = w;
+    for (int l = 1; l < 5; ++l) {
+        hs[l] = (hs[l - 1] + 1) / 2;
+        wsz[l] = (wsz[l - 1] + 1) / 2;
+        const size_t sz = (size_t)n * hs[l] * wsz[l];
+        float* pa = pyr;
+        float* pb = pa + sz;
+        float* pf = pb + sz;
+        pyr = pf + sz + 64;
+        const int grid = ew_grid((long long)sz);
+        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, la[l - 1], pa, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, lb[l - 1], pb, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, lf[l - 1], pf, n, hs[l - 1], wsz[l - 1]);
+        if (int rc = check_launch("metric_msssim pool")) return rc;
+        la[l] = pa;
+        lb[l] = pb;
+        lf[l] = pf;
+    }
+    for (int slot = 0; slot < 6; ++slot) {
+        const int l = slot == 5 ? 0 : slot;
+        const int cs = slot < 4 ? 1 : 0;
+        SsimArgs al{la[l], lb[l], lf[l], n, hs[l], wsz[l], C1, C2, st};
+        if (int rc = run_stats<11>(al, 1.f, 1.f, nullptr, nullptr, 0, cs, nullptr, partial, sums)) return rc;
+        const float inv = 1.f / ((float)(hs[l] - 10) * (float)(wsz[l] - 10));
+        for (int p = 0; p < 2; ++p) hipLaunchKernelGGL(pick_row_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, sums, n, p, inv, out + (p * 6 + slot) * n);
+        if (int rc = check_launch("metric_msssim pick")) return rc;
+    }
+    return MMIF_OK;
+}

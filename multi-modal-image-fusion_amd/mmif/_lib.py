@@ -165,6 +165,16 @@ SIGNATURES = {
     "mmif_ssim_loss_mode_workspace": (_sz, [_i32, _i32, _i32, _i32]),
     "mmif_ssim_loss_mode": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_ssim_terms": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
+    "mmif_metric_moments_workspace": (_sz, [_i32] * 4),
+    "mmif_metric_moments": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "mmif_metric_hist": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mmif_metric_entropy": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "mmif_metric_qabf_workspace": (_sz, [_i32] * 3),
+    "mmif_metric_qabf": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
+    "mmif_metric_vif_workspace": (_sz, [_i32] * 3),
+    "mmif_metric_vif": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "mmif_metric_msssim_workspace": (_sz, [_i32] * 3),
+    "mmif_metric_msssim": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
     "mmif_tv_loss_workspace": (_sz, []),
     "mmif_tv_loss": (_i32, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_pixel_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
