@@ -97,3 +97,93 @@ def load_f19():
                 else:
                     d.update({f"{case}|eval_{k}|{s}|{bits}": v[s, i] for s in range(v.shape[0]) for i, k in enumerate(m["eval"])})
     return d
+
+
+# ------------------------------------------------------------------ sweep inputs (tests/test_gpu_metric_sweep.py against oracle/metric_oracle.py)
+# name -> what it exercises:
+#   int     integer 0..255; f equals a on the left half, so gf == max(ga, gb) ties hit the Nabf / Labf masks
+#   frac    fractional fp32 values
+#   ramp    diamond ramps: Sobel responses in all four quadrants, exact zeros on the symmetry axes and the reflected borders
+#   flat    zero patches in all three images, in f alone and in a alone (VIF's eps branches, Qabf's 0 / 0)
+#   anti    f = 255 - a (negative CC, VIF's g < 0 branch)
+#   same    a == b (g1 == g2 ties of the full VIF)
+#   onebin  every pixel of all three images in bin 100 (entropies 0, normalised MI 0 / 0 = NaN)
+#   edge    fractional values with histogram edge values scattered over all three images
+SWEEP_DISTS = ('int', 'frac', 'ramp', 'flat', 'anti', 'same', 'onebin', 'edge')
+
+_F = np.float32
+# 256.0, -0.0, values in (255, 256), one ulp below integers, the joint histogram's 64-row slab edges, below 0 and above 256
+EDGE_VALUES = np.array([256.0, -0.0, 0.0, 255.0, 255.5, np.nextafter(_F(256), _F(0)), np.nextafter(_F(1), _F(0)), np.nextafter(_F(17), _F(0)),
+                        63.0, 64.0, np.nextafter(_F(64), _F(0)), 127.0, 128.0, np.nextafter(_F(128), _F(0)), 191.0, 192.0,
+                        np.nextafter(_F(192), _F(0)), -3.5, np.nextafter(_F(256), _F(300)), 300.0], np.float32)
+# one ulp below 0 (the smallest negative subnormal) goes to the histogram tests only: next to values of ~100 it is far below half
+# an ulp, so the reference's fp64 Sobel sums keep or absorb it by their summation order, and a gradient component that is exactly
+# 0 (the kernel's exact differences) comes out as -1.4e-45 there, which flips atan2 from +pi to -pi
+TINY_NEG = np.nextafter(_F(0), _F(-1))
+
+
+def _diamond(h, w, cy, cx, sy, sx):
+    y, x = np.mgrid[:h, :w]
+    d = (sy * np.abs(y - cy) + sx * np.abs(x - cx)).astype(np.float32)
+    return d * np.float32(255.0 / max(float(d.max()), 1.0))
+
+
+def sweep_triple(dist, h, w, n=1, seed=0):
+    """(a, b, f) float32 [n,1,h,w] of distribution `dist` (SWEEP_DISTS); the same arguments always give the same arrays"""
+    rng = np.random.default_rng([seed, h, w, n, SWEEP_DISTS.index(dist)])
+    shp = (n, 1, h, w)
+    frac = lambda: (rng.random(shp) * 255.0).astype(np.float32)
+    ints = lambda: rng.integers(0, 256, shp).astype(np.float32)
+    if dist == 'int':
+        a, b = ints(), ints()
+        f = fuse_int(a, b)
+        f[..., :w // 2] = a[..., :w // 2]
+        return a, b, f
+    if dist == 'frac':
+        a, b = frac(), frac()
+        return a, b, (0.6 * a + 0.4 * b).astype(np.float32)
+    if dist == 'ramp':
+        a = _diamond(h, w, h // 2, w // 2, 3, 2)
+        b = _diamond(h, w, h // 3, (2 * w) // 3, 1, 4)
+        f = np.float32(255.0) - _diamond(h, w, (2 * h) // 3, w // 4, 2, 1)
+        return tuple(np.broadcast_to(x, shp).copy() for x in (a, b, f))
+    if dist == 'flat':
+        a, b = frac(), frac()
+        f = (0.5 * a + 0.5 * b).astype(np.float32)
+        for x in (a, b, f):
+            x[..., :h // 3, :w // 3] = 0.0
+        f[..., h // 2:, w // 2:] = 0.0
+        a[..., (2 * h) // 3:, :w // 3] = 0.0
+        return a, b, f
+    if dist == 'anti':
+        a, b = frac(), ints()
+        return a, b, np.float32(255.0) - a
+    if dist == 'same':
+        a = frac()
+        return a, a.copy(), fuse_int(a, a)
+    if dist == 'onebin':
+        return tuple((100.0 + 0.99 * rng.random(shp)).astype(np.float32) for _ in range(3))
+    if dist == 'edge':
+        out = []
+        for x in (frac(), frac(), frac()):
+            m = rng.random(shp) < 0.25
+            x[m] = rng.choice(EDGE_VALUES, int(m.sum()))
+            out.append(x)
+        return tuple(out)
+    raise KeyError(dist)
+
+
+def nonfinite_pair(h, w, n=1, seed=0):
+    """(x, y) float32 [n,1,h,w]: the 'edge' values plus NaN, +-inf and TINY_NEG (only the exact-count histogram test takes these)"""
+    x, _, y = sweep_triple('edge', h, w, n, seed)
+    rng = np.random.default_rng([seed, h, w, n, 99])
+    for t in (x, y):
+        m = rng.random(t.shape) < 0.05
+        t[m] = rng.choice(np.array([np.nan, np.inf, -np.inf, TINY_NEG], np.float32), int(m.sum()))
+    return x, y
+
+
+def mixed_batch(h, w, n, seed=0):
+    """(a, b, f) float32 [n,1,h,w] whose sample i is SWEEP_DISTS[i % 8] (seed + i)"""
+    parts = [sweep_triple(SWEEP_DISTS[i % len(SWEEP_DISTS)], h, w, 1, seed + i) for i in range(n)]
+    return tuple(np.concatenate([p[j] for p in parts]) for j in range(3))
