@@ -22,15 +22,17 @@ struct WinK {
 constexpr int MT_ = 16;   // tile edge
 
 static void make_window(WinK& w, int k) {
-    // core/loss.py:24-39: taps in double -> float32, divided by their float32 sum
+    // core/loss.py:24-39: taps in double -> float32, divided by their float32 sum.  The sum is torch's float32 sum of a short vector:
+    // four interleaved partial sums combined pairwise.  For 5, 7, 9 and 11 taps that is the correctly rounded sum; for 3 taps it is one
+    // ulp above it (golden F20 'msw-ssim_255' shows the difference, tests/test_loss_oracle_cpu.py pins the taps).
     const double sigma = k == 11 ? 1.5 : 0.15 * (k - 1);
     float g[11];
-    double sum = 0.0;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i = 0; i < k; ++i) {
         g[i] = (float)exp(-(double)((i - k / 2) * (i - k / 2)) / (2.0 * sigma * sigma));
-        sum += (double)g[i];
+        acc[i & 3] += g[i];
     }
-    const float fs = (float)sum;
+    const float fs = (acc[0] + acc[1]) + (acc[2] + acc[3]);
     for (int i = 0; i < 11; ++i) w.t[i] = i < k ? g[i] / fs : 0.f;
 }
 
