@@ -322,6 +322,17 @@ int mmif_fuse_attn_bwd(const mmif_tensor* a, const mmif_tensor* b, const mmif_te
 int mmif_fuse_attn_bwd_cached(const mmif_tensor* a, const mmif_tensor* b, const mmif_tensor* g, const mmif_tensor* ga, const mmif_tensor* gb,
                               int32_t mode, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Res2Fusion's non-local spatial attention, spatial_pooling(x, 'nl') of core/fusion.py:96-113, without the [B, H*W, H*W/64] energy
+ * tensor.  x, y, g, dx: plain NCHW fp32 [n][c][h][w]; l: fp32 [n][h*w] (the softmax row sums); scal: 16 words (the global minimum and
+ * maximum of the energy, 1 / (max - min) and the positions of the two extrema), written by fwd and read by bwd.
+ * Limits: 1 <= n <= 65535, 1 <= c <= 256, h, w >= 8, h * w < 2^30; anything else returns MMIF_EINVAL (the workspace query returns 0).
+ * The workspace is scratch: bwd does not need what fwd left in it.  Results are bit-identical from run to run (no atomics). */
+size_t mmif_nonlocal_spatial_workspace(int32_t n, int32_t c, int32_t h, int32_t w);
+int mmif_nonlocal_spatial_fwd(const float* x, float* y, float* l, void* scal, int32_t n, int32_t c, int32_t h, int32_t w, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int mmif_nonlocal_spatial_bwd(const float* x, const float* y, const float* l, const void* scal, const float* g, float* dx, int32_t n, int32_t c,
+                              int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- PFNetv2's self-learned fusion (core/model.py:120-124,134-141): the conv stack ConvLayer(2,2) -> ConvLayer(2,2) ->
  *      ConvLayer(2,1,act=None) applied to every channel pair (feat1[:,i], feat2[:,i]) with SHARED weights.  One "pair conv"
  *      launch replaces the 64 per-channel nn.Conv2d calls of one layer of that Python loop: every channel c of the two

@@ -4,9 +4,12 @@
 element_fusion runs on the HIP element-fusion kernels (mmif_fuse_elem_{fwd,bwd}); inside the models
 concat_fusion is zero-copy (channel-block views) and DenseFuse's 'sum' runs on blocked buffers.
 attention_fusion 'sa' / 'ca' / 'sca' with the reference's default pooling (spatial 'l1', channel 'avg') runs on
-the HIP attention kernels (mmif_fuse_attn_{fwd,bwd}); the remaining pooling modes are tensor-level compositions
-kept for API completeness.
+the HIP attention kernels (mmif_fuse_attn_{fwd,bwd}); spatial 'nl' pooling (Res2Fusion) runs on the streaming non-local kernels
+(mmif_nonlocal_spatial_{fwd,bwd}, no [B, H*W, H*W/64] energy tensor); the remaining pooling modes are tensor-level compositions kept for
+API completeness.
 """
+import os
+
 import torch
 
 from mmif import _lib
@@ -66,6 +69,31 @@ class _AttnFusionFn(torch.autograd.Function):
         return ga.to_nchw(c), gbb.to_nchw(c), None
 
 
+class _NonlocalSpatialFn(torch.autograd.Function):
+    """spatial_pooling(x, 'nl') on csrc/nonlocal.hip: the energy is recomputed tile by tile in both directions; saved for backward are
+    x, y, the softmax row sums l [B, H*W] and the 16-word scalar block (global min / max of the energy and where they sit)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.detach().contiguous()
+        y, l, scal = T.nonlocal_spatial_fwd(x)
+        ctx.save_for_backward(x, y, l, scal)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, l, scal = ctx.saved_tensors
+        return T.nonlocal_spatial_bwd(x, y, l, scal, g.contiguous())
+
+
+def _nonlocal_impl():
+    """$MMIF_NONLOCAL = hip (default) | torch: the streaming kernels, or the tensor-level composition everywhere (cross-check)"""
+    v = os.environ.get("MMIF_NONLOCAL", "hip")
+    if v not in ("hip", "torch"):
+        raise ValueError(f"MMIF_NONLOCAL must be 'hip' or 'torch', got {v!r}")
+    return v
+
+
 def element_fusion(tensor1, tensor2, mode='sum'):
     if mode not in _ELEM_MODES:
         raise ValueError("only supported ['sum', 'mean', 'max'] mode")
@@ -86,7 +114,9 @@ def concat_fusion(tensors, dim=1):
 
 def _nonlocal(t, spatial):
     """Res2Fusion's non-local attention maps (reference core/fusion.py:96-113 spatial, :137-150 channel): softmax over a min-max
-    normalised energy, applied to the features, plus the identity.  Tensor-level composition (two batched matmuls)."""
+    normalised energy, applied to the features, plus the identity.  Tensor-level composition (two batched matmuls): the channel form
+    (energy [B, C, C]) always, the spatial form only where the streaming kernels do not apply (CPU, H or W < 8, C > 256) or under
+    $MMIF_NONLOCAL=torch."""
     b, c, h, w = t.shape
     flat = t.reshape(b, c, -1)
     if spatial:   # queries: every pixel; keys / values: the 8x8 average-pooled map
@@ -112,6 +142,8 @@ def spatial_pooling(tensor, mode='l1'):
     if mode == 'linf':
         return tensor.max(dim=1, keepdim=True)[0]
     if mode == 'nl':
+        if _nonlocal_impl() == 'hip' and T.nonlocal_spatial_supported(tensor):
+            return _NonlocalSpatialFn.apply(tensor)
         return _nonlocal(tensor, spatial=True)
     raise ValueError("only supported ['sum', 'mean', 'l1', 'l2', 'linf', 'nl'] mode")
 

@@ -148,6 +148,9 @@ SIGNATURES = {
     "mmif_fuse_attn_fwd": (_i32, [_TP, _TP, _TP, _i32, _vp, _sz, _vp]),
     "mmif_fuse_attn_bwd": (_i32, [_TP, _TP, _TP, _TP, _TP, _i32, _i32, _vp, _sz, _vp]),
     "mmif_fuse_attn_bwd_cached": (_i32, [_TP, _TP, _TP, _TP, _TP, _i32, _i32, _vp, _sz, _vp]),
+    "mmif_nonlocal_spatial_workspace": (_sz, [_i32] * 4),
+    "mmif_nonlocal_spatial_fwd": (_i32, [_vp] * 4 + [_i32] * 4 + [_vp, _sz, _vp]),
+    "mmif_nonlocal_spatial_bwd": (_i32, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
     "mmif_pairconv_fwd": (_i32, [_TP, _TP, _vp, _vp, _i32, _TP, _TP, _i32, _TP, _TP, _vp]),
     "mmif_pairconv_dgrad": (_i32, [_TP, _TP, _vp, _i32, _TP, _TP, _TP, _TP, _u64, _TP, _vp]),
     "mmif_pairconv_wgrad_workspace": (_sz, []),

@@ -479,6 +479,48 @@ def attn_bwd(a, b, g, ga, gb, mode, accumulate, ws, cached=False):
     check(fn(a.d, b.d, g.d, ga.d, gb.d, mode, int(accumulate), _ptr(ws), ws.numel() * 4, stream_ptr()), "fuse_attn_bwd")
 
 
+# ------------------------------------------------------------------ non-local spatial attention (plain NCHW fp32; csrc/nonlocal.hip)
+NONLOCAL_MAX_C = 256
+NONLOCAL_SCALARS = 16   # words of the scalar block: lo, hi, 1 / (hi - lo), the positions of the two extrema
+
+
+def nonlocal_spatial_supported(x):
+    """CUDA fp32 [B,C,H,W] inside the kernels' limits (include/mmif.h); everything else stays on the tensor-level composition"""
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and 1 <= x.shape[0] <= 65535 and 1 <= x.shape[1] <= NONLOCAL_MAX_C
+            and x.shape[2] >= 8 and x.shape[3] >= 8 and x.shape[2] * x.shape[3] < (1 << 30))
+
+
+def nonlocal_spatial_workspace(x):
+    n, c, h, w = x.shape
+    nbytes = lib.mmif_nonlocal_spatial_workspace(n, c, h, w)
+    if nbytes == 0:
+        raise _lib.MmifError(f"nonlocal_spatial_workspace: {lib.mmif_last_error().decode()}")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+
+
+def nonlocal_spatial_fwd(x):
+    """y = softmax_M(minmax-normalised x^T P) P + x, P = avg_pool2d(x, 8, 8); returns (y, l, scal): the row sums of exp [B, H*W] and the
+    scalar block the backward pass needs"""
+    _f32c(x, "x")
+    n, c, h, w = x.shape
+    y = torch.empty_like(x)
+    l = torch.empty((n, h * w), dtype=torch.float32, device=x.device)
+    scal = torch.empty(NONLOCAL_SCALARS, dtype=torch.float32, device=x.device)
+    ws = nonlocal_spatial_workspace(x)
+    check(lib.mmif_nonlocal_spatial_fwd(_ptr(x), _ptr(y), _ptr(l), _ptr(scal), n, c, h, w, _ptr(ws), ws.numel() * 4, stream_ptr()), "nonlocal_spatial_fwd")
+    return y, l, scal
+
+
+def nonlocal_spatial_bwd(x, y, l, scal, g):
+    _f32c(x, "x"), _f32c(y, "y"), _f32c(l, "l"), _f32c(scal, "scal"), _f32c(g, "g")
+    n, c, h, w = x.shape
+    dx = torch.empty_like(x)
+    ws = nonlocal_spatial_workspace(x)
+    check(lib.mmif_nonlocal_spatial_bwd(_ptr(x), _ptr(y), _ptr(l), _ptr(scal), _ptr(g), _ptr(dx), n, c, h, w, _ptr(ws), ws.numel() * 4, stream_ptr()),
+          "nonlocal_spatial_bwd")
+    return dx
+
+
 def _d(t):
     return t.d if t is not None else None
 
