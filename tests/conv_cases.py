@@ -1,0 +1,498 @@
+"""Cases, fp64 definitions and a restatement of the kernel dispatch for the generic 3x3 / 1x1 ConvLayer kernels (csrc/conv_mfma.hip,
+csrc/conv_x3.hip, csrc/conv_valu.hip, csrc/conv1x1.hip; dispatch in csrc/conv_api.hip).  No GPU needed: tests/test_conv_oracle_cpu.py pins the
+definitions to torch's float64 autograd and the case list to the dispatch; tests/test_gpu_conv_sweep.py runs every case on the device.
+
+The definitions (all float64, on oracle.fusion_oracle):
+
+* forward            y = relu?(b + corr(reflect_pad(x), w))
+* dgrad, padded      gxp[n, c, 0:h+2, 0:w+2] = full scatter of g w  (O.conv2d_reflect_dgrad_padded)
+* dgrad, folded      reflect_pad_adjoint(gxp, 1) in the interior, the ring at zero
+* accumulate bits    bit i of accum_bits ADDS the old contents of channel block i (channels 8i..8i+7) -- gx's own, or gx_old's for
+                     mmif_conv2d_reflect_dgrad_folded_onto
+* mask bits          bit i of mask_bits THEN multiplies block i by [x > 0] (conv_epilogue: `c += old` precedes the mask; conv_api.hip:147
+                     "fold(dgrad(gy)) + gx_old on the blocks in accum_bits, masked by mask_bits").  In the padded domain the mask of a ring
+                     pixel is that of its reflected source, so that folding afterwards equals masking the folded gradient.
+* wgrad              dw[o, c, u, v] = sum g xpad, db[o] = sum g; accumulate adds onto the previous values
+
+bf16 families evaluate the definition on the bf16-rounded x, w, g (and old values) the kernel reads, so the ReLU mask has no near-zero ambiguity.
+"""
+from __future__ import annotations
+
+import zlib
+from dataclasses import dataclass
+
+import numpy as np
+
+from oracle import fusion_oracle as O
+
+ALL = (1 << 64) - 1
+M5A = 0x5a5a5a5a5a5a5a5a
+M33 = 0x3333333333333333
+BIT_SETS = (0, ALL, M5A, M33)
+ALL_BITS = tuple((m, a) for m in BIT_SETS for a in BIT_SETS)          # every combination of mask_bits / accum_bits
+FEW_BITS = ((M5A, M33), (ALL, ALL), (0, 0), (M33, 0))
+
+
+def cdiv(a, b):
+    return (a + b - 1) // b
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the dispatch, restated from conv_mfma() / wgrad_mfma() / launch_conv_dma() (csrc/conv_mfma.hip) and pick_impl() (csrc/conv_api.hip)
+# ------------------------------------------------------------------------------------------------------------------------------
+MT, DT_ROWS, CHUNK_CB = 16, 32, 4
+TN_MAXCB, TN_PL, TN_GROUPS, TN_LOAD = 6, 336, 3, 4
+TNW_GROUPS, TNW_PL, TNW_MAXCB = 2, 324, 8
+TNW_RING = 3 * cdiv(TNW_MAXCB * TNW_PL, 64) * 1024
+C1_MAX_LDS = 128 * 1024
+DEFAULT_SWITCHES = {"conv_dma": 1, "thin_wide": 1, "conv1x1_stream": 1, "wgrad_dma_blocks": 256}     # the mmif_debug_set_* switches
+
+
+def pick_mf(n_out):
+    return min(cdiv(n_out, 16), 4)
+
+
+def n_mblocks(n_out):
+    return cdiv(cdiv(n_out, 16), pick_mf(n_out))
+
+
+def tn_ring_bytes(mf):
+    return {1: 128, 2: 112}.get(mf, 96) * 1024
+
+
+def persistent_grid(num_cus):
+    return max(num_cus // 8 * 8, 8)
+
+
+def pick_mfw(cout):
+    return 1 if cout <= 16 else (2 if cout <= 32 else 4)
+
+
+def pick_icf(ks, cin, cout):
+    return (4 if cin > 32 else (2 if cin > 16 else 1)) if (ks == 1 and pick_mfw(cout) == 4) else 1
+
+
+def wgrad_dma_shape(ks, cin, cout):
+    padded = cdiv(cin, 64) * 64 * cdiv(cout, 64) * 64
+    return ks == 3 and cin % 8 == 0 and cout % 8 == 0 and cin * cout * 10 >= padded * 6
+
+
+def wgrad_taprow_supported(ks, cin, cout):
+    if ks != 3 or cin % 16 or cout % 16:
+        return False
+    nxb, ngb = cin // 16, cout // 16
+    return (ngb == 1 and 1 <= nxb <= 3) or (ngb == 2 and nxb in (2, 4))
+
+
+def wgrad_dma_G(cin, cout, blocks=256):
+    G = blocks // (cdiv(cin, 64) * cdiv(cout, 64))
+    if G >= 8:
+        G = G // 8 * 8
+    return max(G, 1)
+
+
+def wgrad_G(cin, cout, icf=1):
+    mfw = pick_mfw(cout)
+    nb = cdiv(cin, 16 * icf) * cdiv(cout, mfw * 16)
+    G = min((256 * (3 if mfw == 1 else 2)) // nb // 8 * 8, 512)
+    return max(G, 8)
+
+
+def thin_async_ok(dgrad, ks, mf, in_cb, in_halo, in_folded, in_plane, out_hs, out_ws, n, org, num_cus, sw):
+    if not (sw["conv_dma"] == 1 and ks == 3 and mf <= 3 and (dgrad or mf >= 2) and in_cb <= TN_MAXCB
+            and (not dgrad or (in_halo == 1 and in_folded)) and in_plane * 16 * TN_MAXCB < (1 << 31)):
+        return False
+    ntiles = cdiv(out_ws - 2 * org, MT) * cdiv(out_hs - 2 * org, MT) * n
+    slot_bytes = cdiv(cdiv(in_cb * TN_PL, 64), TN_LOAD) * TN_LOAD * 1024
+    return tn_ring_bytes(mf) // slot_bytes >= TN_GROUPS + 1 and 2 * persistent_grid(num_cus) <= ntiles < (1 << 31)
+
+
+def thin_wide_ok(dgrad, ks, mf, in_cb, in_plane, out_hs, out_ws, n, num_cus, sw):
+    if not (sw["thin_wide"] == 1 and sw["conv_dma"] == 1 and not dgrad and ks == 3 and mf == 2 and TN_MAXCB < in_cb <= TNW_MAXCB
+            and in_plane * 16 * TNW_MAXCB < (1 << 31)):
+        return False
+    ntiles = cdiv(out_ws, MT) * cdiv(out_hs, MT) * n
+    return TNW_RING // (cdiv(in_cb * TNW_PL, 64) * 1024) >= TNW_GROUPS + 1 and 2 * persistent_grid(num_cus) <= ntiles < (1 << 31)
+
+
+def conv1x1_stream_ok(sw, in_hs, in_ws, out_hs, out_ws, in_halo, in_folded, in_cb, n_out, m16p, accum_bits):
+    if sw["conv1x1_stream"] == 0 or accum_bits != 0:
+        return False
+    if (in_hs, in_ws) != (out_hs, out_ws) or (in_halo != 0 and not in_folded):
+        return False
+    if m16p > 256 or m16p % 16 or n_out > m16p:
+        return False
+    return cdiv(in_cb, 4) * 4 * m16p * 16 + m16p * 4 <= C1_MAX_LDS
+
+
+def expected_kernel(op, dtype, cin, cout, n, h, w, gy_folded=True, fold=False, mask_bits=0, accum_bits=0, num_cus=256, switches=None, k=3,
+                    impl="auto", gy_halo=1, gx_halo=1):
+    """Name of the kernel the library launches.  op: 'fwd', 'dgrad' (fold = the folded call; '_onto' has the same dispatch), 'wgrad',
+    'bwd_pair', 'bwd_wide' (the input-gradient half; its weight-gradient half is always wgrad_dma), 'dgrad_dup'.  dtype 'bf16' / 'f32';
+    impl 'auto' / 'mfma' / 'x3' / 'valu' (pick_impl: fp32 tensors never reach the bf16 kernels; 'auto' on fp32 takes x3 when the operand image
+    is given, which the cases always do)."""
+    sw = dict(DEFAULT_SWITCHES, **(switches or {}))
+    if dtype == "f32":
+        return "valu" if impl == "valu" else "x3"
+    if impl == "valu":
+        return "valu"
+    if op == "bwd_pair":
+        return "bwd_pair"
+    if op == "wgrad":
+        mfw = pick_mfw(cout)
+        if sw["conv_dma"] == 1 and wgrad_dma_shape(k, cin, cout) and gy_halo == 1 and gy_folded:
+            return "wgrad_dma"
+        if wgrad_taprow_supported(k, cin, cout) and (gy_halo == 0 or gy_folded):
+            return "wgrad_taprow"
+        if k == 3:
+            return f"wgrad_mfma<3,{mfw}>"
+        return f"wgrad_mfma<1,{mfw},2,{pick_icf(1, cin, cout)}>" if mfw == 4 else f"wgrad_mfma<1,{mfw}>"
+    dgrad = op != "fwd"
+    n_out = cin if dgrad else cout
+    n_in = cout if dgrad else cin
+    mf = pick_mf(n_out)
+    in_cb = cdiv(n_in, 8)
+    in_halo = gy_halo if dgrad else 0
+    in_folded = gy_folded if dgrad else False
+    in_hs, in_ws = h + 2 * in_halo, w + 2 * in_halo
+    out_halo = gx_halo if dgrad else 0
+    out_hs, out_ws = h + 2 * out_halo, w + 2 * out_halo
+    if op == "bwd_wide":
+        lmask = mask_bits != 0 and cdiv(in_cb, CHUNK_CB) >= 2
+        return f"conv_dma<L{2 if lmask else 0},org1>"
+    if op == "dgrad_dup":
+        return "conv_dma<L0,org1,dup>"
+    org = 1 if (dgrad and fold and k == 3 and out_halo == 1 and h >= 4 and w >= 4) else 0
+    if k == 1:
+        m16p = n_mblocks(n_out) * mf * 16
+        if conv1x1_stream_ok(sw, in_hs, in_ws, out_hs, out_ws, in_halo, in_folded, in_cb, n_out, m16p, accum_bits):
+            return "conv1x1_stream"
+    if sw["conv_dma"] == 1 and k == 3 and mf == 4 and (not dgrad or (in_halo == 1 and in_folded)) and in_hs * in_ws * 16 * CHUNK_CB < (1 << 31):
+        if not dgrad:
+            return "conv_dma<L0,org0>"
+        lmask = mask_bits != 0 and cdiv(in_cb, CHUNK_CB) >= 2
+        return f"conv_dma<L{1 if lmask else 0},org{org}>"
+    if thin_wide_ok(dgrad, k, mf, in_cb, in_hs * in_ws, out_hs, out_ws, n, num_cus, sw):
+        return "thin_wide"
+    if thin_async_ok(dgrad, k, mf, in_cb, in_halo, in_folded, in_hs * in_ws, out_hs, out_ws, n, org, num_cus, sw):
+        return f"thin_async<{mf}>"
+    return f"mfma<{k},{mf}>"
+
+
+# every kernel name the sweep must reach (tests/test_conv_oracle_cpu.py fails on an unreached one)
+REQUIRED_LABELS = (["mfma<3,%d>" % m for m in (1, 2, 3, 4)] + ["mfma<1,%d>" % m for m in (2, 3, 4)] + ["conv1x1_stream"]
+                   + ["conv_dma<L0,org0>", "conv_dma<L0,org1>", "conv_dma<L1,org0>", "conv_dma<L1,org1>", "conv_dma<L2,org1>", "conv_dma<L0,org1,dup>"]
+                   + ["thin_async<1>", "thin_async<2>", "thin_async<3>", "thin_wide", "wgrad_dma", "wgrad_taprow"]
+                   + ["wgrad_mfma<3,%d>" % m for m in (1, 2, 4)] + ["wgrad_mfma<1,4,2,%d>" % i for i in (1, 2, 4)] + ["bwd_pair", "x3", "valu"])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# cases
+# ------------------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Case:
+    label: str            # the kernel the case is meant to reach at num_cus = 256
+    op: str               # fwd | dgrad | dgrad_onto | wgrad | bwd_pair | bwd_wide | dgrad_dup
+    cin: int
+    cout: int
+    n: int
+    h: int
+    w: int
+    k: int = 3
+    dtype: str = "bf16"
+    impl: str = "mfma"
+    fold: bool = False                # dgrad: the folded call
+    gy_folded: bool = True            # gy is a folded halo-1 gradient (zero ring); False: a padded-domain gradient the kernel folds on load
+    gy_halo: int = 1
+    gx_halo: int = 1
+    bits: tuple = ((0, 0),)           # (mask_bits, accum_bits) pairs run on the one set of operands
+    accumulate: tuple = (0,)          # wgrad family: accumulate flags run
+    relu: bool = True
+    slot: tuple = (0, 0)              # channel blocks before / after the output view inside a wider buffer
+    switches: tuple = ()              # (name, value) pairs of mmif_debug_set_* switches
+    phases: bool = False              # bwd_wide: the two halves as two calls as well
+    note: str = ""
+
+    @property
+    def id(self):
+        s = f"{self.label}-{self.op}{'F' if self.fold else ''}-{self.dtype}-{self.cin}to{self.cout}k{self.k}-{self.n}x{self.h}x{self.w}"
+        if not self.gy_folded:
+            s += "-gyraw"
+        if self.gy_halo == 0:
+            s += "-gyh0"
+        if self.switches:
+            s += "-" + "_".join(f"{a}{b}" for a, b in self.switches)
+        return s + (("-" + self.note) if self.note else "")
+
+    @property
+    def sw(self):
+        return dict(self.switches)
+
+    def expected(self, num_cus=256, mask_bits=None, accum_bits=None):
+        m, a = self.bits[0] if mask_bits is None else (mask_bits, accum_bits)
+        cbm = (1 << cdiv(self.cin, 8)) - 1
+        return expected_kernel("dgrad" if self.op == "dgrad_onto" else self.op, self.dtype, self.cin, self.cout, self.n, self.h, self.w,
+                               self.gy_folded, self.fold, m & cbm, a & cbm, num_cus, self.sw, self.k, self.impl, self.gy_halo, self.gx_halo)
+
+
+NO_DMA = (("conv_dma", 0),)
+REG_MAPS = [(33, 40), (16, 16), (17, 17), (15, 31), (2, 9), (9, 2), (3, 3), (4, 4), (5, 7)]
+REG_CH = [(16, 16), (24, 24), (40, 40), (72, 72), (20, 12), (13, 21)]     # (cin, cout): MF 1..4 both ways + ragged last channel blocks
+
+
+def _cases():
+    cs = []
+    # ---- register-staged conv_mfma_kernel<3, MF>: forward, padded-domain dgrad, folded call (dgrad + stand-alone fold kernel)
+    for cin, cout in REG_CH:
+        for h, w in REG_MAPS:
+            cs.append(Case(f"mfma<3,{pick_mf(cout)}>", "fwd", cin, cout, 3, h, w, switches=NO_DMA))
+            for fold in (False, True):
+                cs.append(Case(f"mfma<3,{pick_mf(cin)}>", "dgrad", cin, cout, 3, h, w, fold=fold, bits=ALL_BITS, switches=NO_DMA))
+        # a padded-domain gy (non-zero ring): the kernel folds it while loading
+        cs.append(Case(f"mfma<3,{pick_mf(cin)}>", "dgrad", cin, cout, 3, 33, 40, gy_folded=False, bits=FEW_BITS, switches=NO_DMA))
+        cs.append(Case(f"mfma<3,{pick_mf(cin)}>", "dgrad", cin, cout, 2, 5, 7, gy_halo=0, bits=FEW_BITS, switches=NO_DMA))
+    # ---- conv_dma_kernel (16 x 32 tiles)
+    dma_maps = [(1, 32, 16), (3, 33, 17), (1, 31, 15), (1, 64, 48), (3, 4, 4), (1, 5, 7)]
+    for cin, cout in [(8, 64), (32, 72), (40, 136), (72, 64)]:
+        for n, h, w in dma_maps:
+            cs.append(Case("conv_dma<L0,org0>", "fwd", cin, cout, n, h, w))
+    for n, h, w in dma_maps:
+        cs.append(Case("conv_dma<L0,org1>", "dgrad", 72, 64, n, h, w, fold=True, bits=((0, M33), (0, 0), (0, ALL)), note="nomask"))
+        cs.append(Case("conv_dma<L1,org1>", "dgrad", 64, 72, n, h, w, fold=True, bits=((M5A, M33), (ALL, 0), (M33, ALL))))
+        cs.append(Case("conv_dma<L1,org1>", "dgrad", 136, 40, n, h, w, fold=True, bits=((M5A, M33), (ALL, ALL))))
+        cs.append(Case("conv_dma<L0,org1>", "dgrad", 64, 32, n, h, w, fold=True, bits=((M5A, M33), (ALL, 0)), note="consumers-fetch-mask"))
+        cs.append(Case("conv_dma<L0,org1>", "dgrad", 72, 8, n, h, w, fold=True, bits=((M5A, M33), (ALL, ALL)), note="consumers-fetch-mask"))
+    for n, h, w in [(3, 33, 17), (1, 5, 7), (2, 3, 5), (2, 5, 3)]:      # org 0: the unfolded call, and the folded call at h = 3 / w = 3
+        fold = h == 3 or w == 3
+        cs.append(Case("conv_dma<L0,org0>", "dgrad", 72, 64, n, h, w, fold=fold, bits=((0, M33), (0, 0))))
+        cs.append(Case("conv_dma<L1,org0>", "dgrad", 64, 72, n, h, w, fold=fold, bits=((M5A, M33), (ALL, 0))))
+        cs.append(Case("conv_dma<L0,org0>", "dgrad", 64, 32, n, h, w, fold=fold, bits=((M5A, M33),), note="consumers-fetch-mask"))
+    # ---- thin_conv_async_kernel: >= 2 * 256 tiles.  8x128x128 = exactly 512; 9x105x131 = 567 (odd: a short last round, tiles of different
+    # images in one block); 2x256x257 = 544; 73x16x112 = 511 tiles stays on the register-staged kernel
+    for cin, cout, n, h, w in [(40, 24, 8, 128, 128), (40, 32, 9, 105, 131), (8, 32, 2, 256, 257), (32, 40, 8, 128, 128), (32, 48, 9, 105, 131),
+                               (24, 40, 9, 121, 125)]:
+        cs.append(Case(f"thin_async<{pick_mf(cout)}>", "fwd", cin, cout, n, h, w))
+    cs.append(Case("mfma<3,2>", "fwd", 40, 24, 73, 16, 112, note="511tiles"))
+    cs.append(Case("mfma<3,3>", "dgrad", 40, 32, 73, 16, 112, fold=True, bits=((M5A, M33),), note="511tiles"))
+    for cin, cout, n, h, w in [(16, 48, 8, 128, 128), (24, 40, 9, 105, 131), (40, 32, 2, 256, 257), (40, 32, 8, 128, 128), (16, 16, 9, 121, 125)]:
+        cs.append(Case(f"thin_async<{pick_mf(cin)}>", "dgrad", cin, cout, n, h, w, fold=True, bits=((M5A, M33), (ALL, 0))))
+        cs.append(Case(f"thin_async<{pick_mf(cin)}>", "dgrad_onto", cin, cout, n, h, w, fold=True, bits=((M5A, M33), (0, ALL))))
+    cs.append(Case("thin_async<2>", "dgrad", 24, 40, 8, 128, 128, fold=False, bits=((M5A, M33),), note="padded-domain"))   # org 0: 9x9 tiles of the 130x130 stored map
+    # ---- the wide 64 -> 32 forward geometry, output slot inside a wider buffer
+    cs.append(Case("thin_wide", "fwd", 64, 32, 8, 128, 128, slot=(1, 1)))
+    cs.append(Case("thin_wide", "fwd", 56, 24, 3, 250, 180, slot=(1, 2)))
+    # ---- weight gradients
+    for acc in ((0, 1),):
+        for cin, cout, n, h, w in [(64, 136, 3, 33, 17), (304, 152, 2, 33, 40), (304, 152, 1, 16, 16), (64, 64, 1, 16, 16), (128, 64, 1, 64, 48)]:
+            cs.append(Case("wgrad_dma", "wgrad", cin, cout, n, h, w, accumulate=acc))
+        cs.append(Case("wgrad_dma", "wgrad", 64, 136, 3, 33, 17, accumulate=acc, switches=(("wgrad_dma_blocks", 64),)))
+        cs.append(Case("wgrad_dma", "wgrad", 128, 64, 1, 64, 48, accumulate=acc, switches=(("wgrad_dma_blocks", 64),)))
+        for cin, cout in [(16, 16), (48, 16), (32, 32), (64, 32)]:
+            for n, h, w in [(3, 33, 40), (1, 16, 16), (2, 5, 7)]:
+                cs.append(Case("wgrad_taprow", "wgrad", cin, cout, n, h, w, accumulate=acc))
+        for cin, cout in [(20, 12), (13, 21), (72, 64), (40, 40)]:
+            for n, h, w in [(3, 33, 40), (1, 16, 16), (2, 2, 9), (3, 17, 17)]:
+                cs.append(Case(f"wgrad_mfma<3,{pick_mfw(cout)}>", "wgrad", cin, cout, n, h, w, accumulate=acc))
+        for cin, cout in [(8, 64), (24, 40), (88, 64)]:
+            for n, h, w in [(3, 33, 40), (1, 16, 16)]:
+                cs.append(Case(f"wgrad_mfma<1,4,2,{pick_icf(1, cin, cout)}>", "wgrad", cin, cout, n, h, w, k=1, accumulate=acc))
+    # ---- one-launch backward of a thin layer / of a wide layer, straight against the definition
+    for cin, cout in [(64, 32), (32, 16)]:
+        for n, h, w in [(3, 33, 40), (1, 4, 4), (1, 64, 48)]:
+            cs.append(Case("bwd_pair", "bwd_pair", cin, cout, n, h, w, bits=((ALL, 0),), accumulate=(0, 1)))
+    for cin, cout in [(64, 64), (128, 64), (64, 128)]:
+        for n, h, w in [(3, 33, 17), (1, 4, 4), (1, 64, 48)]:
+            cs.append(Case("conv_dma<L2,org1>", "bwd_wide", cin, cout, n, h, w, bits=((ALL, 0), (M5A, 0)), accumulate=(0, 1), phases=(h == 33)))
+    cs.append(Case("conv_dma<L0,org1>", "bwd_wide", 64, 64, 3, 33, 17, bits=((0, 0),), note="nomask"))
+    for n, h, w in [(2, 33, 40), (1, 4, 4), (1, 64, 48)]:
+        cs.append(Case("conv_dma<L0,org1,dup>", "dgrad_dup", 64, 64, n, h, w, fold=True))
+    # ---- fp32 tensors: the split-operand (x3) and the fp32 FMA (valu) kernels; one map per tile-edge class
+    for impl in ("x3", "valu"):
+        for cin, cout in [(16, 16), (48, 16), (72, 64), (13, 21)]:
+            for n, h, w in [(2, 33, 40), (1, 16, 16), (2, 17, 17), (2, 2, 9), (1, 3, 3), (2, 5, 7)]:
+                cs.append(Case(impl, "fwd", cin, cout, n, h, w, dtype="f32", impl=impl))
+                cs.append(Case(impl, "dgrad", cin, cout, n, h, w, dtype="f32", impl=impl, fold=True, bits=FEW_BITS))
+                cs.append(Case(impl, "wgrad", cin, cout, n, h, w, dtype="f32", impl=impl, accumulate=(0, 1)))
+            cs.append(Case(impl, "dgrad", cin, cout, 2, 33, 40, dtype="f32", impl=impl, fold=False, bits=FEW_BITS))
+    for cin, cout in [(72, 64), (13, 21)]:      # x3 dgrad masked by the sign map its weight gradient leaves
+        cs.append(Case("x3", "bwd_wide", cin, cout, 2, 33, 40, dtype="f32", impl="x3", bits=((ALL, 0), (M5A, 0)), accumulate=(0, 1)))
+    # ---- 1x1 layers
+    for cin, cout in [(8, 64), (88, 64), (24, 40)]:
+        for n, h, w in [(3, 33, 40), (1, 16, 16), (2, 5, 7)]:
+            cs.append(Case("conv1x1_stream", "fwd", cin, cout, n, h, w, k=1))
+            cs.append(Case("conv1x1_stream", "dgrad", cin, cout, n, h, w, k=1, gy_halo=0, gx_halo=0, bits=((M5A, 0), (0, 0))))
+            # accumulate bits: the streaming kernel declines, conv_mfma_kernel<1, MF> runs
+            cs.append(Case(f"mfma<1,{pick_mf(cin)}>", "dgrad", cin, cout, n, h, w, k=1, gy_halo=0, gx_halo=0, bits=((M5A, M33), (0, ALL))))
+    for cin, cout in [(40, 24), (24, 40), (88, 64)]:
+        cs.append(Case(f"mfma<1,{pick_mf(cout)}>", "fwd", cin, cout, 3, 33, 40, k=1, switches=(("conv1x1_stream", 0),)))
+    return cs
+
+
+CASES = _cases()
+assert len({c.id for c in CASES}) == len(CASES), "duplicate case ids"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# operands and definitions
+# ------------------------------------------------------------------------------------------------------------------------------
+def rnd(a, dtype):
+    """the values a tensor of the case's dtype holds, as float64"""
+    a = np.asarray(a, np.float32)
+    return (O.bf16_round(a) if dtype == "bf16" else a).astype(np.float64)
+
+
+@dataclass
+class Operands:
+    x: np.ndarray
+    w: np.ndarray         # what the kernel multiplies with: bf16-rounded for the bf16 families (packed operand images are bf16)
+    w32: np.ndarray       # the fp32 master weights handed to the library
+    b: np.ndarray
+    g: np.ndarray         # upstream gradient, logical [n, cout, h, w] (for gy_folded=False cases: the fold of gp)
+    gp: np.ndarray        # stored gradient [n, cout, h+2*halo, w+2*halo]
+    old: np.ndarray       # previous contents of gx (stored extent)
+    dw_old: np.ndarray
+    db_old: np.ndarray
+    F: np.ndarray = None  # dgrad_dup: the 128-channel activations whose blocks 6, 7 / 14, 15 mask the copies
+    key: tuple = ()
+
+
+_OPS = {}      # the last few operand sets / definitions only: cases that share one are neighbours in CASES
+_KEEP = 3
+
+
+def _put(d, key, val):
+    d[key] = val
+    while len(d) > _KEEP * (1 if d is _OPS else 4):
+        d.pop(next(iter(d)))
+    return val
+
+
+def operands(c: Case) -> Operands:
+    key = (c.dtype, c.cin, c.cout, c.k, c.n, c.h, c.w, c.gy_folded, c.gy_halo, c.gx_halo, c.op == "dgrad_dup")
+    if key in _OPS:
+        return _OPS[key]
+    rng = np.random.default_rng(zlib.crc32(repr(key).encode()))
+    x = rnd(rng.standard_normal((c.n, c.cin, c.h, c.w)), c.dtype)
+    w32 = (rng.standard_normal((c.cout, c.cin, c.k, c.k)) * 0.05).astype(np.float32)
+    w = rnd(w32, c.dtype)
+    b = rng.standard_normal(c.cout).astype(np.float32).astype(np.float64)
+    hg = c.gy_halo
+    gp = rnd(rng.standard_normal((c.n, c.cout, c.h + 2 * hg, c.w + 2 * hg)), c.dtype)
+    if hg and c.gy_folded:
+        ring = np.ones(gp.shape[2:], bool)
+        ring[1:-1, 1:-1] = False
+        gp[:, :, ring] = 0.0
+    if hg and not c.gy_folded:      # the kernel folds a padded-domain gy while loading: "fp32 fold, rounded once" (csrc/conv_mfma.hip load_in_gradfold)
+        g = rnd(O.reflect_pad_adjoint(gp, 1), c.dtype)
+    else:
+        g = gp[:, :, 1:-1, 1:-1] if hg else gp
+    hx = c.gx_halo
+    old = rnd(rng.standard_normal((c.n, c.cin, c.h + 2 * hx, c.w + 2 * hx)), c.dtype)
+    dw_old = (rng.standard_normal(w.shape) * np.sqrt(c.n * c.h * c.w)).astype(np.float32).astype(np.float64)
+    db_old = (rng.standard_normal(c.cout) * np.sqrt(c.n * c.h * c.w)).astype(np.float32).astype(np.float64)
+    F = rnd(rng.standard_normal((c.n, 128, c.h, c.w)), c.dtype) if c.op == "dgrad_dup" else None
+    return _put(_OPS, key, Operands(x, w, w32, b, np.ascontiguousarray(g), gp, old, dw_old, db_old, F, key))
+
+
+def block_mask(bits, channels):
+    """per-channel 0/1 vector of a 64-bit channel-block set"""
+    return np.array([(bits >> (ch // 8)) & 1 for ch in range(channels)], np.float64)
+
+
+def ring_zero(a):
+    a = a.copy()
+    a[:, :, 0] = 0
+    a[:, :, -1] = 0
+    a[:, :, :, 0] = 0
+    a[:, :, :, -1] = 0
+    return a
+
+
+_DEF = {}
+
+
+def _cached(key, fn):
+    if key not in _DEF:
+        _put(_DEF, key, fn())
+    return _DEF[key]
+
+
+def def_fwd(c: Case):
+    """(y, S): the definition and the same sum on |operands| (the scale of the fp32 accumulation error)"""
+    o = operands(c)
+
+    def go():
+        y = O.conv2d_reflect_fwd(o.x, o.w, o.b, c.relu)
+        S = O.conv2d_reflect_fwd(np.abs(o.x), np.abs(o.w), np.abs(o.b), False)
+        return y, S
+    return _cached(("fwd", o.key, c.relu), go)
+
+
+def def_dgrad_padded(c: Case):
+    """(gxp, Sp) on the stored extent of gx: padded domain for k = 3 with a halo, the plain map for halo 0 / 1x1 inside its ring"""
+    o = operands(c)
+
+    def go():
+        gxp = O.conv2d_reflect_dgrad_padded(o.g, o.w)
+        Sp = O.conv2d_reflect_dgrad_padded(np.abs(o.g), np.abs(o.w))
+        return gxp, Sp
+    return _cached(("gxp", o.key), go)
+
+
+def def_dgrad(c: Case, mask_bits, accum_bits, old=None):
+    """Definition of one dgrad call on gx's stored extent [n, cin, h+2*halo, w+2*halo]: returns (ref, S, parts) -- parts = the padded-domain
+    values before the fold (None where nothing is folded), for the rounding bound of the dgrad + stand-alone-fold path.
+    Folded call: interior = (fold(gxp) + old) * mask, ring = 0.  Padded call: (gxp + old) * reflect_pad(mask)."""
+    o = operands(c)
+    old = o.old if old is None else old
+    gxp, Sp = def_dgrad_padded(c)
+    am = block_mask(accum_bits, c.cin)[None, :, None, None]
+    mm = block_mask(mask_bits, c.cin)[None, :, None, None]
+    pos = (o.x > 0).astype(np.float64)
+    p = c.k // 2
+    hx = c.gx_halo
+    if c.k == 1 or hx == 0:          # nothing outside the interior is computed; a halo ring (1x1 with halo 1) keeps its contents
+        core = gxp if p == 0 else O.reflect_pad_adjoint(gxp, p)
+        Score = Sp if p == 0 else O.reflect_pad_adjoint(Sp, p)
+        keep = 1 - mm + mm * pos
+        ref = old.copy()
+        S = np.abs(old).copy()
+        inner = (slice(None), slice(None), slice(hx, hx + c.h), slice(hx, hx + c.w))
+        ref[inner] = (core + am * old[inner]) * keep
+        S[inner] = Score + am * np.abs(old[inner])
+        return ref, S, None
+    keep_p = 1 - mm + mm * O.reflect_pad(pos, 1)
+    if not c.fold:
+        return (gxp + am * old) * keep_p, Sp + am * np.abs(old), None
+    oldz = ring_zero(old)            # the folded call's contract: gx's ring is zero on entry
+    parts = (gxp + am * oldz) * keep_p
+    ref = np.zeros_like(gxp)
+    ref[:, :, 1:-1, 1:-1] = O.reflect_pad_adjoint(parts, 1)
+    S = np.zeros_like(gxp)
+    S[:, :, 1:-1, 1:-1] = O.reflect_pad_adjoint(Sp + am * np.abs(oldz), 1)
+    A_fold = np.zeros_like(gxp)
+    A_fold[:, :, 1:-1, 1:-1] = O.reflect_pad_adjoint(np.abs(parts), 1)
+    return ref, S, A_fold
+
+
+def def_wgrad(c: Case, accumulate):
+    o = operands(c)
+
+    def go():
+        _, gw, gb = O.conv2d_reflect_bwd(o.x, o.w, None, o.g, relu=False, need_gx=False)
+        return gw, gb
+    gw, gb = _cached(("wgrad", o.key), go)
+    return (gw + o.dw_old, gb + o.db_old) if accumulate else (gw, gb)
+
+
+def K_terms(c: Case):
+    """number of products accumulated into one output"""
+    return c.k * c.k * (c.cin if c.op == "fwd" else c.cout)
+
+
+def bf16_bound(c: Case, A, S, extra_terms=2):
+    """|got - ref| <= 2^-8 A + (K + 2) 2^-24 S: A = the sum of the magnitudes of the values the path stores in bf16 on the way to this element
+    (one round-to-nearest each: half an ulp of an 8-bit significand is 2^-8 of the value just above a power of two, 2^-9 just below the next --
+    2^-8 is attained, the bound has no slack there), S = the same sum on |operands| (+ |b| / |old|), K = the number of fp32-accumulated terms
+    (bf16 x bf16 products are exact in fp32; each addition rounds to 2^-24 of a partial sum that S bounds)."""
+    return 2.0 ** -8 * A + (K_terms(c) + extra_terms) * 2.0 ** -24 * S

@@ -68,10 +68,14 @@ def test_conv_bf16_vs_oracle_on_rounded_operands(case, impl):
 
 
 DMA_SHAPES = [(128, 128, 2, 37, 53), (176, 112, 1, 64, 48), (72, 64, 2, 33, 40), (64, 184, 1, 40, 72), (96, 96, 3, 16, 16)]
+# thin layers that stay on the register-staged kernel in both modes of the switch: fewer than 512 tiles of 16x16 (468 and 432), and
+# 48 -> 48 (six input channel blocks leave the three-fragment kernel's ring fewer than four tile slots)
+DMA_SHAPES += [(16, 16, 3, 180, 200), (16, 48, 3, 178, 190), (48, 48, 2, 241, 275)]
 # thin layers (<= 48 channels either side) take the asynchronous loader/consumer kernel once a persistent block owns at least
-# two tiles: >= 512 tiles of 16x16
-DMA_SHAPES += [(16, 16, 3, 180, 200), (48, 16, 2, 250, 270), (16, 48, 3, 178, 190), (32, 16, 2, 256, 256), (24, 40, 2, 257, 300),
-               (48, 48, 2, 241, 275), (8, 16, 2, 256, 300)]
+# two tiles: >= 512 tiles of 16x16 on a 256-CU part (asserted through conv_cases.expected_kernel below)
+THIN_ASYNC_SHAPES = [(48, 16, 2, 250, 270), (32, 16, 2, 256, 256), (24, 40, 2, 257, 300), (8, 16, 2, 256, 300),
+                     (16, 16, 3, 208, 224), (16, 48, 3, 208, 224)]
+DMA_SHAPES += THIN_ASYNC_SHAPES
 # NestFuse's decoder / encoder 3x3 layers (reference core/block.py:836-867: channel counts that are not multiples of 64 -- ragged last
 # M-block in forward (Cout) and dgrad (Cin), ragged 64-channel groups in the weight gradient, which skips the staging of their padded planes)
 DMA_SHAPES += [(304, 152, 1, 48, 40), (176, 88, 2, 33, 48), (272, 136, 1, 40, 56), (240, 120, 1, 64, 32), (384, 192, 1, 32, 48), (368, 184, 1, 36, 44),
@@ -88,7 +92,13 @@ def test_dma_staged_kernels_equal_register_staged(cin, cout, n, h, w):
     use the same MFMA order -> bit identical; wgrad sums tiles in a different order -> 2e-5."""
     from mmif import tensor as T
     from mmif._lib import IMPL_MFMA, lib
+    from conv_cases import expected_kernel
     dev = "cuda:0"
+    if (cin, cout, n, h, w) in THIN_ASYNC_SHAPES:   # the folded gy of this test: forward by Cout, the padded-domain dgrad by Cin
+        ncu = torch.cuda.get_device_properties(0).multi_processor_count
+        took = (expected_kernel("fwd", "bf16", cin, cout, n, h, w, num_cus=ncu), expected_kernel("dgrad", "bf16", cin, cout, n, h, w, True, False,
+                                                                                                   1, 1, ncu))
+        assert any(t.startswith("thin_async") for t in took), f"listed as a thin asynchronous shape, but mode 1 takes {took} with {ncu} compute units"
     torch.manual_seed(cin * 7 + cout)
     x = T.BT.alloc(n, cin, h, w, torch.bfloat16, dev); x.buf.normal_()
     gy = T.BT.alloc(n, cout, h, w, torch.bfloat16, dev, halo=1, zero=True); gy.buf[:, :, 1:-1, 1:-1].normal_()
