@@ -593,7 +593,7 @@ void mmif_debug_set_thin_wide(int32_t mode);
  * encoder's backward (round 5's side-stream experiment, measured and closed: DESIGN.md section 4.1).  Results change in the last bits only (the per-block partial sums regroup). */
 void mmif_debug_set_wgrad_dma_blocks(int32_t blocks);
 /* Weight gradients of 3x3 layers whose channel counts are not multiples of 64 (round 6; NestFuse's 88 / 120 / 136 / 152 / 184 / 304-channel
- * layers): 1 (default, $MMIF_WGRAD_RAGGED) = wgrad_dma_kernel does not stage the channel-block planes of a ragged last group that lie past the
+ * layers): 1 (default) = wgrad_dma_kernel does not stage the channel-block planes of a ragged last group that lie past the
  * tensor (their products are never reduced), 0 = it re-reads the last real plane for them as before.  Identical dW / db either way. */
 void mmif_debug_set_ragged(int32_t mode);
 /* Deferred weight-gradient reductions (round 5, csrc/reduce_defer.hip).  Every weight-gradient entry point above ends in a small fixed-order

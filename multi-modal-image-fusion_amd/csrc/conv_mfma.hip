@@ -1704,7 +1704,7 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
         // Ragged last channel group (round 6; NestFuse: 152 = 64 + 64 + 24 output, 304 = 4 x 64 + 48 input channels): the pieces that hold
         // only planes past the tensor are not requested at all -- the kernel runs at the rate its tiles are staged (74 KB per tile and block,
         // ~4.4 TB/s over the chip, measured round 6), and those pieces used to re-read the last real plane.  The consumers multiply whatever
-        // the slots hold: those dW rows / columns and db entries are never reduced.  ($MMIF_WGRAD_RAGGED=0 stages them as before)
+        // the slots hold: those dW rows / columns and db entries are never reduced.  (mmif_debug_set_ragged(0) stages them as before)
         const int px_end = ragged_skip ? (min(8, tx.cb - icg * 8) * WG_XPL + 63) / 64 : WD_XPIECES;
         const int pg_end = WD_XPIECES + (ragged_skip ? (min(8, tg.cb - ocg * 8) * WG_GPL + 63) / 64 : WD_GPIECES);
         auto issue = [&](int tile, int buf) {
@@ -2643,7 +2643,7 @@ static int g_taprow_mode = -1;   // $MMIF_WGRAD_TAPROW=0: keep the per-input-gro
 size_t wgrad_mfma_workspace(int cin, int cout, int ks) {
     const int mfw = pick_mfw(cout), icf = pick_icf(ks, cin, cout);
     size_t a = 0;
-    for (int f = 1; f <= icf; f *= 2) {   // (either block width may run: $MMIF_WGRAD1X1_WIDE)
+    for (int f = 1; f <= icf; f *= 2) {   // (either block width may run)
         const size_t per = (size_t)mfw * 16 * 16 * f * ks * ks + mfw * 16;
         const size_t b = (size_t)wgrad_G(cin, cout, f) * cdiv(cin, 16 * f) * cdiv(cout, mfw * 16) * per * sizeof(float);
         if (b > a) a = b;

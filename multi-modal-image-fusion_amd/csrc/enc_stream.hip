@@ -310,7 +310,7 @@ extern "C" int mmif_dense_encoder_fwd_sum(const mmif_dense_encoder* enc_a, const
     MMIF_REQUIRE(sum->dtype == MMIF_BF16 && sum->halo == 0 && sum->cb == 8 && sum->n == out_a->n && sum->h == out_a->h && sum->w == out_a->w,
                  "dense_encoder_fwd_sum: sum must be a bf16 halo-0 view of 8 channel blocks of the branches' shape");
     MMIF_REQUIRE(mmif_dense_encoder_fwd_sum_supported(enc_a, enc_b, out_a->n, out_a->h, out_a->w),
-                 "dense_encoder_fwd_sum: the two branches must share ONE set of weights (and $MMIF_ENC_STREAM2 must not be 0)");
+                 "dense_encoder_fwd_sum: the two branches must share ONE set of weights (and mmif_debug_set_enc_stream2(0) must not be in force)");
     EncArgs A;
     memset(&A, 0, sizeof(A));
     for (int b = 0; b < 2; ++b) {
@@ -345,7 +345,7 @@ extern "C" int mmif_dense_encoder_fwd(const mmif_dense_encoder* enc_a, const mmi
     }
     A.n = out_a->n; A.h = out_a->h; A.w = out_a->w;
     A.relu0 = 1;
-    // round 5: the 64-column input-stationary kernel (csrc/enc_stream2.hip); $MMIF_ENC_STREAM2=0 / mmif_debug_set_enc_stream2(0): this file's
+    // round 5: the 64-column input-stationary kernel (csrc/enc_stream2.hip); mmif_debug_set_enc_stream2(0): this file's
     if (enc_stream2_ok(A, nb)) return enc_stream2_launch(A, nb, (hipStream_t)stream);
     es_geometry(A.n, A.h, A.w, nb, A.nstrips, A.nseg, A.seg_rows);
     A.items = A.n * A.nseg * A.nstrips;

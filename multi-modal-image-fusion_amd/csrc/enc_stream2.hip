@@ -26,7 +26,7 @@
 // Rounding points are the layer-wise kernels' (every x_k rounded to bf16 once, fp32 accumulation), the accumulation ORDER is not, so
 // the results are no longer bit-identical to them: tests/test_gpu_enc_stream.py holds this kernel to the fp64 definition of every stage
 // on the kernel's own bf16 inputs at one bf16 rounding (as tests/test_gpu_enc_chain.py does for the backward chain).  x0 (fp32 FMAs in
-// the old order) stays bit-identical.  $MMIF_ENC_STREAM2=0 selects the round-2 kernel.
+// the old order) stays bit-identical.  mmif_debug_set_enc_stream2(0) selects the round-2 kernel.
 #include "enc_stream.hpp"
 #include <stdlib.h>
 #pragma clang diagnostic ignored "-Winline-asm"   // (the LDS-DMA asm names m0 in its clobber list: "reserved register")

@@ -32,8 +32,6 @@ FLAT_BUFFERS = {}
 FRESH_LEAVES = [None]
 # bumped by every fused optimiser step: the packed bf16 weight images must be rebuilt
 WEIGHTS_EPOCH = [0]
-# id()s of pooled scratch buffers whose addresses are baked into a captured hipGraph (never evicted from their pools)
-GRAPH_PINNED = set()
 GRAD_TAIL = 8  # scalar slots after the gradients (loss values ride along in the gradient all-reduce)
 
 
@@ -55,21 +53,20 @@ def set_compute_dtype(dtype):
 
 
 # A/B switches ($MMIF_...): read from the environment ONCE and cached -- the per-step host path only looks them up in this dict.  A process
-# that changes one at run time (the tests do) calls reload_switches().
+# that changes one at run time (the tests do) calls reload_switches().  Every switch and its default ("0" in the environment = off, anything
+# else = on): all but two select the newer of two bit-identical routes and are on.
 _SW = {}
+SWITCH_DEFAULTS = dict.fromkeys(
+    ("MMIF_ENC_STREAM", "MMIF_ENC_SUM", "MMIF_ENC_BWD_FUSED", "MMIF_ENC_CHAIN", "MMIF_ENC_CHAIN_STREAM", "MMIF_ENC_WGRAD", "MMIF_BWD_PAIR",
+     "MMIF_BWD_WIDE", "MMIF_IMAGE_BWD", "MMIF_FUSE_SHARE", "MMIF_DGRAD_DUP", "MMIF_PAIR_BWD"), "1")
+SWITCH_DEFAULTS["MMIF_DEFER_REDUCE"] = "0"     # measured no faster: ModelEngine.defer_reduces
+SWITCH_DEFAULTS["MMIF_X3_LAYERS"] = "0"        # stand-alone fp32 ConvLayers stay on the exact FMA kernels: wants_packed
 
 
-def switch(name, default="1"):
+def switch(name):
     v = _SW.get(name)
     if v is None:
-        v = _SW[name] = os.environ.get(name, default) != "0"
-    return v
-
-
-def switch_int(name, default):
-    v = _SW.get(name)
-    if v is None:
-        v = _SW[name] = int(os.environ.get(name, str(default)))
+        v = _SW[name] = os.environ.get(name, SWITCH_DEFAULTS[name]) != "0"     # (KeyError: a switch nobody declared)
     return v
 
 
@@ -112,7 +109,7 @@ def wants_packed(dtype, impl, standalone=False):
         return False
     if dtype == torch.bfloat16:
         return True
-    if standalone and impl != _lib.IMPL_X3 and not switch("MMIF_X3_LAYERS", "0"):
+    if standalone and impl != _lib.IMPL_X3 and not switch("MMIF_X3_LAYERS"):
         return False
     return x3_enabled()
 
@@ -206,6 +203,33 @@ class ConvSpec:
         else:
             self.dw[:, :self.split] = t[:, cu:]
             self.dw[:, self.split:] = t[:, :cu]
+
+
+def conv_spec(name, layer, split=0):
+    """the ConvSpec of a core.block ConvLayer: its conv is layers[0], and it has a ReLU exactly when it has an activation"""
+    return ConvSpec(name, layer.layers[0], layer.act is not None, split)
+
+
+class DenseSpecs(list):
+    """The four ConvSpecs of one encoder (Conv + DenseBlock) with the two facts the fused encoder kernels ask of them, worked out once (the
+    specs never change): `canonical` = the 3x3 layers 1 -> 16, 16 -> 16, 32 -> 16, 48 -> 16 those kernels are written for; `all_relu` =
+    every layer has its ReLU, which only the two fused forward routes (enc_fwd_all, enc_fwd_sum) also require.  Whatever depends on dtype,
+    impl, shape or a switch is asked per call."""
+
+    def __init__(self, specs):
+        super().__init__(specs)
+        self.canonical = all(s.k == 3 for s in self) and [(s.cin, s.cout) for s in self] == [(1, 16), (16, 16), (32, 16), (48, 16)]
+        self.all_relu = all(s.relu for s in self)
+
+
+def pin_for_graph(bt):
+    """mark a pooled scratch buffer whose address is baked into a captured hipGraph: its pool never evicts it.  The mark sits on the
+    buffer's own tensor, so it cannot outlive the buffer or pass to another one"""
+    bt.buf.graph_pinned = True
+
+
+def graph_pinned(bt):
+    return getattr(bt.buf, "graph_pinned", False)
 
 
 class Lease:
@@ -311,7 +335,7 @@ class ModelEngine:
         measured at the headline size, the one launch takes 29 us against 32 us for the five it replaces -- a reduce right after its producer
         reads the partial sums (113 MB for decode.0) out of the last-level cache, the deferred one reads 220 MB from HBM after the other
         backward kernels have evicted them."""
-        if not switch("MMIF_DEFER_REDUCE", "0"):
+        if not switch("MMIF_DEFER_REDUCE"):
             return False
         need = 0
         for s in layers:
@@ -527,8 +551,7 @@ class DenseEncoderMixin:
         """branches: [(specs, img, first channel block in F), ...] (one or two).  bf16 / MFMA: ONE streaming launch for all four
         layers of all branches (csrc/enc_stream.hip; bit-identical to the layer-wise launches, $MMIF_ENC_STREAM=0 selects those)."""
         stream = (dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and switch("MMIF_ENC_STREAM")
-                  and all(s.relu and s.k == 3 for specs, _, _ in branches for s in specs)
-                  and all([(s.cin, s.cout) for s in specs] == [(1, 16), (16, 16), (32, 16), (48, 16)] for specs, _, _ in branches))
+                  and all(specs.canonical and specs.all_relu for specs, _, _ in branches))
         if not stream:
             for specs, img, base in branches:
                 DenseEncoderMixin.enc_fwd(specs, img, F, base, impl)
@@ -564,22 +587,21 @@ class DenseEncoderMixin:
         if gz is None:
             gz = BT.alloc(F.n, 64, F.h, F.w, torch.bfloat16, F.buf.device)
             # bounded (variable-size crops grew this without limit): the least recently used shapes go once more than 8 are held --
-            # except those a live GraphedStep captured (mmif/graph.py pins the buffers of its capture in GRAPH_PINNED)
+            # except those handed out during a graph capture (pinned below)
             while len(pool) >= 8:
-                victim = next((k for k in pool if id(pool[k].buf) not in GRAPH_PINNED), None)
+                victim = next((k for k in pool if not graph_pinned(pool[k])), None)
                 if victim is None:
                     break
                 del pool[victim]
         pool[key] = gz          # (re-inserted last = most recently used)
         if torch.cuda.is_current_stream_capturing():
-            GRAPH_PINNED.add(id(gz.buf))
+            pin_for_graph(gz)
         return gz
 
     @staticmethod
     def chain_streams(specs, F, impl):
         """this encoder's backward chain runs as the streaming launch (csrc/enc_chain.hip)"""
-        return (F.dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and all(s.k == 3 for s in specs)
-                and [(s.cin, s.cout) for s in specs] == [(1, 16), (16, 16), (32, 16), (48, 16)]
+        return (F.dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and specs.canonical
                 and F.h >= 4 and F.w >= 4 and switch("MMIF_ENC_CHAIN") and switch("MMIF_ENC_CHAIN_STREAM"))
 
     @staticmethod
@@ -590,8 +612,7 @@ class DenseEncoderMixin:
         if not (switch("MMIF_ENC_BWD_FUSED") and switch("MMIF_ENC_CHAIN") and switch("MMIF_ENC_CHAIN_STREAM") and switch("MMIF_ENC_WGRAD")
                 and F.dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and F.h >= 4 and F.w >= 4 and F.halo == 0
                 and all(_lib.lib.mmif_dense_encoder_bwd_fits(t.cb_total, t.h, t.w, t.halo) for br in branches for t in (F, br[3], br[4]))
-                and all(all(s.k == 3 for s in specs) and [(s.cin, s.cout) for s in specs] == [(1, 16), (16, 16), (32, 16), (48, 16)]
-                        for specs, *_ in branches)):
+                and all(specs.canonical for specs, *_ in branches)):
             return False
         args = []
         if len(branches) == 2:
@@ -647,11 +668,9 @@ class DenseEncoderMixin:
         GF = GF.as_folded()   # every contribution so far has been folded; each dgrad below re-folds what it adds
         # bf16 / MFMA: the four layers' weight gradients in ONE pass over [x0 | x1 | x2] and the finished [g0 | g1 | g2 | g3]
         # (csrc/enc_wgrad.hip; $MMIF_ENC_WGRAD=0 selects the layer-wise kernels)
-        hot = (F.dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and all(s.k == 3 for s in specs)
-               and [(s.cin, s.cout) for s in specs] == [(1, 16), (16, 16), (32, 16), (48, 16)])
+        hot = F.dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and specs.canonical
         # fp32 on the split-operand kernels: the same fused weight-gradient call (wgrad_x3_dense_kernel); the dgrad chain stays per layer
-        hot32 = (F.dtype == torch.float32 and impl != _lib.IMPL_VALU and x3_enabled() and all(s.k == 3 for s in specs)
-                 and [(s.cin, s.cout) for s in specs] == [(1, 16), (16, 16), (32, 16), (48, 16)] and F.halo == 0)
+        hot32 = F.dtype == torch.float32 and impl != _lib.IMPL_VALU and x3_enabled() and specs.canonical and F.halo == 0
         fused = (hot or hot32) and switch("MMIF_ENC_WGRAD")
         # ... and the dgrad chain per DESTINATION (gather form: one launch per x_k on the stacked virtual layer, fp32 sum of all
         # contributions, one rounding) instead of per source layer (read-modify-write of the lower blocks); $MMIF_ENC_CHAIN=0: scatter
@@ -692,28 +711,25 @@ class DenseEncoderMixin:
         else:
             T.image_in_wgrad(img, gz.view(0, 2), first.dw, first.db, first.cout, first.k, ws, accumulate_w)
 
+    def enc_bwd_all(self, branches, F, GF, ws, impl, onto=None):
+        """The backward of one or two encoder branches, [(specs, img, first channel block of the branch in F and GF), ...]; GF holds
+        dL/d(encoder outputs) as enc_bwd takes it (onto: as there, for every branch).  The whole of it as ONE launch (bwd_fused) where that
+        applies; else the gradient chains of two branches as one launch where that applies (chain_all), then enc_bwd per branch.  A second
+        branch that shares its specs (ONE encoder applied to both images) accumulates its weight gradients onto the first's."""
+        gf = GF.as_folded()
+        acc = [k > 0 and specs is branches[0][0] for k, (specs, _, _) in enumerate(branches)]
+        if self.bwd_fused([(specs, img, base, gf.view(base + 6, 2), onto.view(0, 6) if onto is not None else gf.view(base, 6), a)
+                           for (specs, img, base), a in zip(branches, acc)], F, ws, impl):
+            return
+        gz = self.chain_all([(specs, base, base, onto) for specs, _, base in branches], F, GF, impl)
+        for (specs, img, base), a, z in zip(branches, acc, gz):
+            self.enc_bwd(specs, img, F, GF, base, base, ws, impl, accumulate_w=a, onto=onto, gz=z)
 
-class PFNetv1Engine(ModelEngine, DenseEncoderMixin):
-    """reference core/model.py:69-111."""
-
-    def __init__(self, module):
-        m = module
-        def cs(name, layer):
-            return ConvSpec(name, layer.layers[0], layer.act is not None)
-        self.enc = []
-        for e, seq in enumerate((m.encode1, m.encode2)):
-            self.enc.append([cs(f"encode{e + 1}.0", seq[0])] + [cs(f"encode{e + 1}.1.{i}", l) for i, l in enumerate(seq[1].layers)])
-        self.dec = [cs(f"decode.{i}", l) for i, l in enumerate(m.decode)]
-        super().__init__(module, self.enc[0] + self.enc[1] + self.dec)
-
-    def forward(self, img1, img2):
-        (img1, img2), n, h, w, dtype, impl = self.prepare((img1, img2))
-        dev = img1.device
-        L = self.lease((n, h, w, dtype), dev)
-        L.imgs = (img1, img2)
-        F = self.buf(L, "F", n, 128, h, w, dtype, dev)
-        self.enc_fwd_all([(self.enc[0], img1, 0), (self.enc[1], img2, 8)], F, dtype, impl)
-        x = F
+    # the decoder every dense net ends in: 3x3 ConvLayers self.dec, the last one the image layer (Cout = 1) ------------------------
+    def dec_fwd(self, L, x, impl):
+        """the decoder on the features x; activations into the lease's D{i}, returns the fp32 image"""
+        n, h, w, dtype = L.key[:4]
+        dev = x.buf.device
         for i, s in enumerate(self.dec[:-1]):
             y = self.buf(L, f"D{i}", n, s.cout, h, w, dtype, dev)
             self.c_fwd(s, x, y, impl)
@@ -722,21 +738,24 @@ class PFNetv1Engine(ModelEngine, DenseEncoderMixin):
         out = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
         T.image_out_fwd(x, last.w.detach(), last.b.detach(), out, last.cin, last.k, last.relu)
         L.out = out.detach() if last.relu else None     # (an alias: the returned object gets a grad_fn, which must not be kept alive by the lease)
-        return out, L
+        return out
 
-    def backward(self, L, gout):
-        n, h, w, dtype = L.key
+    def dec_bwd(self, L, gout, x0, mask0, dup=None):
+        """The decoder's backward, from the image's gradient gout down to the gradient of x0, the features dec_fwd was given.  mask0: the
+        channel blocks of x0 whose ReLU mask decode.0's dgrad applies (those with no further contributor; the others are masked by their
+        last contributor in the encoder's backward).  dup(L, s, x, g, gx, ws, impl): another route for decode.0's backward, which returns
+        the folded gradient or None when it does not apply (DenseFuse.dgrad_dup).
+        Returns (gradient of x0, did dup run, workspace, impl, the parameters' gradient views for autograd)."""
+        n, h, w, dtype = L.key[:4]
         dev = gout.device
         impl = conv_impl()
         flat, grads = self._assign_grad_views(dev)
         ws = self.workspace(dev)
-        img1, img2 = L.imgs
-        F = L.bufs["F"]
-        acts = [F] + [L.bufs[f"D{i}"] for i in range(len(self.dec) - 1)]
+        acts = [x0] + [L.bufs[f"D{i}"] for i in range(len(self.dec) - 1)]
         last = self.dec[-1]
         x = acts[-1]
-        # the decoder's weight-gradient reduces as ONE launch at the end of the decoder's backward (not with the side-stream experiment: its
-        # producer runs on another stream)
+        dup_ran = False
+        # the decoder's weight-gradient reduces as ONE launch at the end of the decoder's backward
         deferred = dtype == torch.bfloat16 and self.defer_reduces(dev, self.dec)
         try:      # (a failing launch must not leave the library's deferred-reduce queue open: ADVICE r5)
             g = self.buf(L, f"G{len(acts) - 1}", n, last.cin, h, w, dtype, dev, halo=1)
@@ -747,9 +766,12 @@ class PFNetv1Engine(ModelEngine, DenseEncoderMixin):
                 if i > 0 and self.pair_ok(s, dtype, impl, h, w):
                     g = self.c_bwd_pair(s, g, x, gx, ws)      # thin layer: dgrad (every block masked) + wgrad in one launch
                     continue
-                # gradient w.r.t. the concatenated encoder features (i == 0): only each encoder's last DenseBlock output
-                # (blocks 6,7 / 14,15) has no further contributor
-                mb = all_bits(gx.cb) if i > 0 else bits(6, 7, 14, 15)
+                if i == 0 and dup is not None:
+                    gd = dup(L, s, x, g, gx, ws, impl)
+                    if gd is not None:
+                        g, dup_ran = gd, True
+                        continue
+                mb = all_bits(gx.cb) if i > 0 else mask0
                 if self.wide_ok(s, dtype, impl, x, gx):
                     g = self.c_bwd_wide(s, g, x, gx, mb, ws)  # wide layer: the wgrad leaves the ReLU sign bytes the dgrad masks with
                     continue
@@ -759,38 +781,48 @@ class PFNetv1Engine(ModelEngine, DenseEncoderMixin):
             if deferred:
                 self.flush_reduces()
         self.early_reduce(flat, self.dec)      # (data parallel) the decoder's gradients leave while the encoder's backward runs
-        self.enc_bwd_all(img1, img2, F, g, ws, impl)
-        return grads
+        return g, dup_ran, ws, impl, grads
 
-    def enc_bwd_all(self, img1, img2, F, g, ws, impl):
-        gf = g.as_folded()
-        if self.bwd_fused([(self.enc[0], img1, 0, gf.view(6, 2), gf.view(0, 6), False), (self.enc[1], img2, 8, gf.view(14, 2), gf.view(8, 6), False)], F, ws, impl):
-            return
-        gz = self.chain_all([(self.enc[0], 0, 0, None), (self.enc[1], 8, 8, None)], F, g, impl)
-        self.enc_bwd(self.enc[0], img1, F, g, 0, 0, ws, impl, gz=gz[0])
-        self.enc_bwd(self.enc[1], img2, F, g, 8, 8, ws, impl, gz=gz[1])
+
+class PFNetv1Engine(ModelEngine, DenseEncoderMixin):
+    """reference core/model.py:69-111."""
+
+    def __init__(self, module):
+        m = module
+        self.enc = [DenseSpecs([conv_spec(f"encode{e + 1}.0", seq[0])] + [conv_spec(f"encode{e + 1}.1.{i}", l) for i, l in enumerate(seq[1].layers)])
+                    for e, seq in enumerate((m.encode1, m.encode2))]
+        self.dec = [conv_spec(f"decode.{i}", l) for i, l in enumerate(m.decode)]
+        super().__init__(module, self.enc[0] + self.enc[1] + self.dec)
+
+    def forward(self, img1, img2):
+        (img1, img2), n, h, w, dtype, impl = self.prepare((img1, img2))
+        dev = img1.device
+        L = self.lease((n, h, w, dtype), dev)
+        L.imgs = (img1, img2)
+        F = self.buf(L, "F", n, 128, h, w, dtype, dev)
+        self.enc_fwd_all([(self.enc[0], img1, 0), (self.enc[1], img2, 8)], F, dtype, impl)
+        return self.dec_fwd(L, F, impl), L
+
+    def backward(self, L, gout):
+        img1, img2 = L.imgs
+        F = L.bufs["F"]
+        # gradient w.r.t. the concatenated encoder features: only each encoder's last DenseBlock output (blocks 6,7 / 14,15) has no
+        # further contributor
+        g, _, ws, impl, grads = self.dec_bwd(L, gout, F, bits(6, 7, 14, 15))
+        self.enc_bwd_all([(self.enc[0], img1, 0), (self.enc[1], img2, 8)], F, g, ws, impl)
+        return grads
 
 
 class VIFNetEngine(PFNetv1Engine):
     """reference core/model.py:189-206: PFNetv1's graph with ONE encoder applied to both images (its weight gradients are
-    the sum of the two branches: the second branch accumulates)."""
+    the sum of the two branches: the second branch accumulates, enc_bwd_all)."""
 
     def __init__(self, module):
         m = module
-        def cs(name, layer):
-            return ConvSpec(name, layer.layers[0], layer.act is not None)
-        shared = [cs("encode.0", m.encode[0])] + [cs(f"encode.1.{i}", l) for i, l in enumerate(m.encode[1].layers)]
+        shared = DenseSpecs([conv_spec("encode.0", m.encode[0])] + [conv_spec(f"encode.1.{i}", l) for i, l in enumerate(m.encode[1].layers)])
         self.enc = [shared, shared]
-        self.dec = [cs(f"decode.{i}", l) for i, l in enumerate(m.decode)]
+        self.dec = [conv_spec(f"decode.{i}", l) for i, l in enumerate(m.decode)]
         ModelEngine.__init__(self, module, shared + self.dec)
-
-    def enc_bwd_all(self, img1, img2, F, g, ws, impl):
-        gf = g.as_folded()
-        if self.bwd_fused([(self.enc[0], img1, 0, gf.view(6, 2), gf.view(0, 6), False), (self.enc[1], img2, 8, gf.view(14, 2), gf.view(8, 6), True)], F, ws, impl):
-            return
-        gz = self.chain_all([(self.enc[0], 0, 0, None), (self.enc[1], 8, 8, None)], F, g, impl)
-        self.enc_bwd(self.enc[0], img1, F, g, 0, 0, ws, impl, accumulate_w=False, gz=gz[0])
-        self.enc_bwd(self.enc[1], img2, F, g, 8, 8, ws, impl, accumulate_w=True, gz=gz[1])
 
 
 class DenseFuseEngine(ModelEngine, DenseEncoderMixin):
@@ -801,10 +833,8 @@ class DenseFuseEngine(ModelEngine, DenseEncoderMixin):
 
     def __init__(self, module):
         m = module
-        def cs(name, layer):
-            return ConvSpec(name, layer.layers[0], layer.act is not None)
-        self.enc = [cs("encode.0", m.encode[0])] + [cs(f"encode.1.{i}", l) for i, l in enumerate(m.encode[1].layers)]
-        self.dec = [cs(f"decode.{i}", l) for i, l in enumerate(m.decode)]
+        self.enc = DenseSpecs([conv_spec("encode.0", m.encode[0])] + [conv_spec(f"encode.1.{i}", l) for i, l in enumerate(m.encode[1].layers)])
+        self.dec = [conv_spec(f"decode.{i}", l) for i, l in enumerate(m.decode)]
         super().__init__(module, self.enc + self.dec)
 
     def forward(self, img1, img2):
@@ -822,93 +852,49 @@ class DenseFuseEngine(ModelEngine, DenseEncoderMixin):
             if not self.enc_fwd_sum(img1, img2, F, x, dtype, impl):
                 self.enc_fwd_all([(self.enc, img1, 0), (self.enc, img2, 8)], F, dtype, impl)
                 self.fusion_fwd(L, F, x)
-        for i, s in enumerate(self.dec[:-1]):
-            y = self.buf(L, f"D{i}", n, s.cout, h, w, dtype, dev)
-            self.c_fwd(s, x, y, impl)
-            x = y
-        last = self.dec[-1]
-        out = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
-        T.image_out_fwd(x, last.w.detach(), last.b.detach(), out, last.cin, last.k, last.relu)
-        L.out = out.detach() if last.relu else None     # (an alias: the returned object gets a grad_fn, which must not be kept alive by the lease)
-        return out, L
+        return self.dec_fwd(L, x, impl), L
 
     def backward(self, L, gout):
-        n, h, w, dtype, single = L.key
-        dev = gout.device
-        impl = conv_impl()
-        flat, grads = self._assign_grad_views(dev)
-        ws = self.workspace(dev)
-        img1, img2 = L.imgs
+        single = L.key[4]
         F = L.bufs["F"]
-        first_in = F if single else L.bufs["S"]
-        acts = [first_in] + [L.bufs[f"D{i}"] for i in range(len(self.dec) - 1)]
-        last = self.dec[-1]
-        x = acts[-1]
-        # the decoder's weight-gradient reduces as ONE launch at the end of the decoder's backward (not with the side-stream experiment: its
-        # producer runs on another stream)
-        deferred = dtype == torch.bfloat16 and self.defer_reduces(dev, self.dec)
-        try:
-            g = self.buf(L, f"G{len(acts) - 1}", n, last.cin, h, w, dtype, dev, halo=1)
-            g = self.image_layer_bwd(last, x, gout, L.out, g, ws)
-            for i in range(len(self.dec) - 2, -1, -1):
-                s, x = self.dec[i], acts[i]
-                gx = self.buf(L, f"G{i}", n, s.cin, h, w, dtype, dev, halo=1)
-                if i > 0 and self.pair_ok(s, dtype, impl, h, w):
-                    g = self.c_bwd_pair(s, g, x, gx, ws)
-                    continue
-                # i == 0: the auto-encoder's input is the DenseBlock output (only its last conv, blocks 6,7, has no further contributor);
-                # x = f1 + f2 is not a ReLU output
-                mb = all_bits(gx.cb) if i > 0 else (bits(6, 7) if single else 0)
-                if i == 0 and not single and self.dup_ok(s, g, gx, L, dtype, impl):
-                    # 'sum' fusion: decode.0's dgrad also leaves the copies of its blocks 6, 7 that each encoder branch masks with its own x3
-                    # (csrc/conv_mfma.hip struct DupOut, round 6: mmif_fuse_elem_bwd's launch disappears); the weight gradient apart
-                    GF = self.buf(L, "GF", n, 128, h, w, dtype, dev, halo=1)
-                    self.c_wgrad(s, x, g, ws, impl)
-                    g = T.conv_dgrad_dup(g, gx, s.cin, s.cout, s.k, s.packed, GF, F, 3, s.name + ":dgrad")
-                    L.dup_done = True
-                    continue
-                if self.wide_ok(s, dtype, impl, x, gx):
-                    g = self.c_bwd_wide(s, g, x, gx, mb, ws)
-                    continue
-                self.c_wgrad(s, x, g, ws, impl)
-                g = self.c_dgrad(s, g, x, gx, mb, 0, impl)
-        finally:
-            if deferred:
-                self.flush_reduces()
-        self.early_reduce(flat, self.dec)
-        return self._encoder_backward(L, F, g, ws, impl, dtype, dev, n, h, w, single, img1, img2, grads)
-
-    def _encoder_backward(self, L, F, g, ws, impl, dtype, dev, n, h, w, single, img1, img2, grads):
         if single:
-            gf = g.as_folded()
-            if not self.bwd_fused([(self.enc, img1, 0, gf.view(6, 2), gf.view(0, 6), False)], F, ws, impl):
-                self.enc_bwd(self.enc, img1, F, g, 0, 0, ws, impl)
-            return grads
+            # the auto-encoder's input is the DenseBlock output: only its last conv (blocks 6,7) has no further contributor
+            g, dup_ran, ws, impl, grads = self.dec_bwd(L, gout, F, bits(6, 7))
+        else:
+            # x = f1 + f2 is not a ReLU output: nothing to mask
+            g, dup_ran, ws, impl, grads = self.dec_bwd(L, gout, L.bufs["S"], 0, dup=self.dgrad_dup)
+        self._encoder_backward(L, F, g, ws, impl, dup_ran)
+        return grads
+
+    def dgrad_dup(self, L, s, x, g, gx, ws, impl):
+        """'sum' fusion: decode.0's dgrad also leaves the copies of its blocks 6, 7 that each encoder branch masks with its own x3
+        (csrc/conv_mfma.hip struct DupOut, round 6: mmif_fuse_elem_bwd's launch disappears); the weight gradient apart.  None = not taken."""
+        n, h, w, dtype = L.key[:4]
+        if not self.dup_ok(s, g, gx, L, dtype, impl):
+            return None
+        GF = self.buf(L, "GF", n, 128, h, w, dtype, gx.buf.device, halo=1)
+        self.c_wgrad(s, x, g, ws, impl)
+        return T.conv_dgrad_dup(g, gx, s.cin, s.cout, s.k, s.packed, GF, L.bufs["F"], 3, s.name + ":dgrad")
+
+    def _encoder_backward(self, L, F, g, ws, impl, dup_ran):
+        """dup_ran: decode.0's dgrad already left the masked top blocks of both branches in GF (dgrad_dup)"""
+        n, h, w, dtype, single = L.key
+        img1, img2 = L.imgs
+        if single:
+            return self.enc_bwd_all([(self.enc, img1, 0)], F, g, ws, impl)
         # fusion backward: d(f1+f2) -> each encoder's own gradient buffer (they diverge below);
         # ReLU mask only on the DenseBlock's last conv output (blocks 6,7), the rest are masked by
         # their last contributor inside enc_bwd
-        GF = self.buf(L, "GF", n, 128, h, w, dtype, dev, halo=1)
+        GF = self.buf(L, "GF", n, 128, h, w, dtype, g.buf.device, halo=1)
+        branches = [(self.enc, img1, 0), (self.enc, img2, 8)]
         if self.share_fused_grad(g, GF, dtype, impl):
             # 'sum' fusion: d(f1 + f2) IS each branch's gradient.  Only the masked top blocks (6,7 / 14,15) are materialised per branch;
             # the chain reads the lower blocks' starting values straight from g ($MMIF_FUSE_SHARE=0: copy them per branch first)
-            if not getattr(L, "dup_done", False):     # (decode.0's dgrad left them already: dup_ok)
+            if not dup_ran:
                 T.fuse_elem_bwd(F.view(6, 2), F.view(14, 2), g.view(6, 2), GF.view(6, 2), GF.view(14, 2), self.fusion_mode, True)
-            L.dup_done = False
-            gff = GF.as_folded()
-            if self.bwd_fused([(self.enc, img1, 0, gff.view(6, 2), g.view(0, 6), False), (self.enc, img2, 8, gff.view(14, 2), g.view(0, 6), True)], F, ws, impl):
-                return grads
-            gz = self.chain_all([(self.enc, 0, 0, g), (self.enc, 8, 8, g)], F, GF, impl)
-            self.enc_bwd(self.enc, img1, F, GF, 0, 0, ws, impl, accumulate_w=False, onto=g, gz=gz[0])
-            self.enc_bwd(self.enc, img2, F, GF, 8, 8, ws, impl, accumulate_w=True, onto=g, gz=gz[1])
-            return grads
+            return self.enc_bwd_all(branches, F, GF, ws, impl, onto=g)
         self.fusion_bwd(L, F, g, GF, ws)
-        gff = GF.as_folded()
-        if self.bwd_fused([(self.enc, img1, 0, gff.view(6, 2), gff.view(0, 6), False), (self.enc, img2, 8, gff.view(14, 2), gff.view(8, 6), True)], F, ws, impl):
-            return grads
-        gz = self.chain_all([(self.enc, 0, 0, None), (self.enc, 8, 8, None)], F, GF, impl)
-        self.enc_bwd(self.enc, img1, F, GF, 0, 0, ws, impl, accumulate_w=False, gz=gz[0])
-        self.enc_bwd(self.enc, img2, F, GF, 8, 8, ws, impl, accumulate_w=True, gz=gz[1])
-        return grads
+        self.enc_bwd_all(branches, F, GF, ws, impl)
 
     def enc_fwd_sum(self, img1, img2, F, S, dtype, impl):
         """bf16, 'sum' fusion: the shared encoder on both images AND f1 + f2 as ONE launch (csrc/enc_stream2.hip's dual form, round 6;
@@ -916,7 +902,7 @@ class DenseFuseEngine(ModelEngine, DenseEncoderMixin):
         specs = self.enc
         if not (dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and switch("MMIF_ENC_STREAM") and switch("MMIF_ENC_SUM")
                 and type(self).fusion_fwd is DenseFuseEngine.fusion_fwd and self.fusion_mode == _lib.FUSE_SUM
-                and all(s.relu and s.k == 3 for s in specs) and [(s.cin, s.cout) for s in specs] == [(1, 16), (16, 16), (32, 16), (48, 16)]):
+                and specs.canonical and specs.all_relu):
             return False
         br = [(img, specs[0].w.detach(), specs[0].b.detach(), [s.packed for s in specs[1:]], [s.b.detach() for s in specs[1:]], F.view(base, 8))
               for img, base in ((img1, 0), (img2, 8))]
@@ -932,9 +918,7 @@ class DenseFuseEngine(ModelEngine, DenseEncoderMixin):
         return self.share_fused_grad(gx, GF, dtype, impl)
 
     def share_fused_grad(self, g, GF, dtype, impl):
-        specs = self.enc
-        hot = (dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and all(s.k == 3 for s in specs)
-               and [(s.cin, s.cout) for s in specs] == [(1, 16), (16, 16), (32, 16), (48, 16)])
+        hot = dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and self.enc.canonical
         return (hot and type(self).fusion_bwd is DenseFuseEngine.fusion_bwd and self.fusion_mode == _lib.FUSE_SUM
                 and switch("MMIF_ENC_CHAIN") and switch("MMIF_FUSE_SHARE")
                 and all(T.dgrad_onto_supported(GF.as_folded().view(2 * (k + 1), 2 * (3 - k)), GF.view(2 * k, 2), 16, 16 * (3 - k), 3)
@@ -957,7 +941,7 @@ class PFNetv2Engine(DenseFuseEngine):
 
     def __init__(self, module):
         super().__init__(module)
-        self.fuse = [ConvSpec(f"fuse.{i}", l.layers[0], l.act is not None) for i, l in enumerate(module.fuse)]
+        self.fuse = [conv_spec(f"fuse.{i}", l) for i, l in enumerate(module.fuse)]
         for s in self.fuse:
             assert (s.cin, s.k) == (2, 3) and s.cout in (1, 2), "PFNetv2.fuse layers are 3x3 convs on channel pairs"
             s.pair = True

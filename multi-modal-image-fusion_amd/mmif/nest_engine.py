@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from . import tensor as T
-from .engine import ConvSpec, ModelEngine, all_bits, bits, conv_impl
+from .engine import ModelEngine, all_bits, bits, conv_impl, conv_spec
 
 
 def rng_bits(lo, n):
@@ -26,24 +26,20 @@ class NestEngine(ModelEngine):
     def __init__(self, module, rfn):
         m = module
         self.rfn = rfn
-
-        def cs(name, layer, split=0):
-            return ConvSpec(name, layer.layers[0], layer.act is not None, split)
-
-        self.conv_in = cs("conv_in", m.conv_in)
-        self.cb = [(cs(f"CB{i + 1}_0.0", b.layers[0]), cs(f"CB{i + 1}_0.1", b.layers[1])) for i, b in enumerate((m.CB1_0, m.CB2_0, m.CB3_0, m.CB4_0))]
+        self.conv_in = conv_spec("conv_in", m.conv_in)
+        self.cb = [(conv_spec(f"CB{i + 1}_0.0", b.layers[0]), conv_spec(f"CB{i + 1}_0.1", b.layers[1])) for i, b in enumerate((m.CB1_0, m.CB2_0, m.CB3_0, m.CB4_0))]
         c = self.CH
         d = m.decode
         # (block, split = channels of the non-upsampled part of its concat)
-        self.db = {k: (cs(f"decode.{k}.0", getattr(d, k).layers[0], split), cs(f"decode.{k}.1", getattr(d, k).layers[1]))
+        self.db = {k: (conv_spec(f"decode.{k}.0", getattr(d, k).layers[0], split), conv_spec(f"decode.{k}.1", getattr(d, k).layers[1]))
                    for k, split in (("DB1_1", c[0]), ("DB2_1", c[1]), ("DB3_1", c[2]), ("DB1_2", 2 * c[0]), ("DB2_2", 2 * c[1]), ("DB1_3", 3 * c[0]))}
-        self.conv_out = cs("conv_out", m.conv_out)
+        self.conv_out = conv_spec("conv_out", m.conv_out)
         specs = [self.conv_in] + [s for p in self.cb for s in p] + [s for p in self.db.values() for s in p] + [self.conv_out]
         self.rfns = []
         if rfn:
             for i, r in enumerate((m.RFN1, m.RFN2, m.RFN3, m.RFN4)):
-                d_ = dict(res=cs(f"RFN{i + 1}.res", r.res), conv1=cs(f"RFN{i + 1}.conv1", r.conv1), conv2=cs(f"RFN{i + 1}.conv2", r.conv2),
-                          l0=cs(f"RFN{i + 1}.layers.0", r.layers[0]), l1=cs(f"RFN{i + 1}.layers.1", r.layers[1]), l2=cs(f"RFN{i + 1}.layers.2", r.layers[2]))
+                d_ = dict(res=conv_spec(f"RFN{i + 1}.res", r.res), conv1=conv_spec(f"RFN{i + 1}.conv1", r.conv1), conv2=conv_spec(f"RFN{i + 1}.conv2", r.conv2),
+                          l0=conv_spec(f"RFN{i + 1}.layers.0", r.layers[0]), l1=conv_spec(f"RFN{i + 1}.layers.1", r.layers[1]), l2=conv_spec(f"RFN{i + 1}.layers.2", r.layers[2]))
                 self.rfns.append(d_)
                 specs += list(d_.values())
         super().__init__(module, specs)

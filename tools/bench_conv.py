@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Time one conv layer's fwd / dgrad (bf16 MFMA kernels) and check the DMA-staged kernel against the register-staged one.
-usage: bench_conv.py cin cout B S [iters]"""
+usage: bench_conv.py cin cout B S [iters] [dma]     dma = 1 (default): the DMA-staged kernels, 0: the register-staged ones
+(mmif_debug_set_conv_dma); a run compares its results with those the other mode's last run left in /tmp"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "multi-modal-image-fusion_amd")]
 import torch
 from mmif import tensor as T
-from mmif._lib import IMPL_MFMA
+from mmif._lib import IMPL_MFMA, lib
 cin, cout, B, S = [int(a) for a in (sys.argv[1:5] + ["128", "128", "32", "256"][len(sys.argv) - 1:])]
 iters = int(sys.argv[5]) if len(sys.argv) > 5 else 20
 dev = "cuda:0"
@@ -33,10 +34,11 @@ def timeit(kind):
     for _ in range(iters): run(kind)
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters
-mode = os.environ.get("MMIF_CONV_DMA", "1")
+mode = sys.argv[6] if len(sys.argv) > 6 else "1"
+lib.mmif_debug_set_conv_dma(int(mode))
 for kind in ("fwd", "dgrad", "wgrad"):
     ms = timeit(kind)
-    print(f"MMIF_CONV_DMA={mode} {kind} {cin}->{cout} B={B} {S}x{S}: {ms:.3f} ms  {flops / ms / 1e9:.0f} TFLOP/s")
+    print(f"conv_dma={mode} {kind} {cin}->{cout} B={B} {S}x{S}: {ms:.3f} ms  {flops / ms / 1e9:.0f} TFLOP/s")
 torch.save({"y": y.buf.cpu(), "gx": gx.buf.cpu(), "dw": dw.cpu(), "db": db.cpu()}, f"/tmp/conv_out_{mode}.pt")
 other = f"/tmp/conv_out_{'0' if mode != '0' else '1'}.pt"
 if os.path.isfile(other):
