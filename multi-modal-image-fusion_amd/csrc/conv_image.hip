@@ -3,8 +3,7 @@
 // ConvLayer(16,1,act=None) :86,131,179 / ConvLayer(64,1,ksize=1) :344.  Images are fp32 [n][h][w].
 // These layers are HBM-bound (K = 9 or M = 1): plain VALU kernels, fp32 math, T only on the
 // feature-map side.
-#include "common.hpp"
-#include "reduce_defer.hpp"
+#include "wgrad_reduce.hpp"
 
 namespace mmif {
 
@@ -62,7 +61,7 @@ typedef float f32x2_i __attribute__((ext_vector_type(2)));
 template <typename T, int KS>
 __global__ __launch_bounds__(256) void image_in_wgrad_kernel(const float* __restrict__ img, TV tg, float* __restrict__ partial,
                                                              int cout, long long npix) {
-    constexpr int KK = KS * KS, P = KS / 2, PER = 16 * KK + 16, HALF = 8 * KK + 8;
+    constexpr int KK = KS * KS, P = KS / 2, PER = image_in_wgrad_reduce<KS>::PER, HALF = 8 * KK + 8;
     __shared__ float red[4][HALF];
     const int tid = threadIdx.x, cb = blockIdx.y, n_og = (gridDim.y + 1) / 2;
     f32x2_i acc[4][KK], accb[4];
@@ -122,31 +121,6 @@ __global__ __launch_bounds__(256) void image_in_wgrad_kernel(const float* __rest
         else dst[16 * KK + (cb & 1) * 8 + (e - 8 * KK)] = t;
     }
     (void)cout;
-}
-
-template <int KS>
-__global__ __launch_bounds__(64 * RED_SLICES) void image_in_wgrad_reduce(const float* __restrict__ partial, float* __restrict__ dw,
-                                                             float* __restrict__ db, int cout, int G, int n_og, int accumulate) {
-    constexpr int KK = KS * KS, PER = 16 * KK + 16;
-    __shared__ float red[RED_SLICES][64];
-    const int o_local = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int idx = blockIdx.x * 64 + o_local;
-    long long off = 0;
-    bool valid = false;
-    if (idx < cout * KK) {
-        const int o = idx / KK, tap = idx % KK;
-        off = (long long)(o / 16) * PER + (o % 16) * KK + tap;
-        valid = true;
-    } else if (idx < cout * KK + cout) {
-        const int o = idx - cout * KK;
-        off = (long long)(o / 16) * PER + 16 * KK + (o % 16);
-        valid = true;
-    }
-    const float t = partial_sum(partial, off, (long long)n_og * PER, G, valid, red);
-    if (slice == 0 && valid) {
-        if (idx < cout * KK) dw[idx] = accumulate ? dw[idx] + t : t;
-        else if (db) db[idx - cout * KK] = accumulate ? db[idx - cout * KK] + t : t;
-    }
 }
 
 // ---------------------------------------------------------------- Cout == 1 forward
@@ -301,7 +275,7 @@ __global__ __launch_bounds__(256) void image_out_dgrad_kernel(const float* __res
 template <typename T, int KS>
 __global__ __launch_bounds__(256) void image_out_wgrad_kernel(TV tx, const float* __restrict__ gimg, const float* __restrict__ yimg,
                                                               float* __restrict__ partial, long long npix) {
-    constexpr int KK = KS * KS, P = KS / 2, PER = 16 * KK + 1, HALF = 8 * KK + 1;
+    constexpr int KK = KS * KS, P = KS / 2, PER = image_out_wgrad_reduce<KS>::PER, HALF = 8 * KK + 1;
     __shared__ float red[4][HALF];
     const int tid = threadIdx.x, cb = blockIdx.y, n_cg = (gridDim.y + 1) / 2;
     f32x2_i acc[4][KK];
@@ -374,38 +348,7 @@ __global__ __launch_bounds__(256) void image_out_wgrad_kernel(TV tx, const float
     (void)npix;
 }
 
-template <int KS>
-__global__ __launch_bounds__(64 * RED_SLICES) void image_out_wgrad_reduce(const float* __restrict__ partial, float* __restrict__ dw,
-                                                              float* __restrict__ db, int cin, int G, int n_cg, int accumulate) {
-    constexpr int KK = KS * KS, PER = 16 * KK + 1;
-    __shared__ float red[RED_SLICES][64];
-    const int o_local = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int idx = blockIdx.x * 64 + o_local;
-    long long off = 0;
-    bool valid = false;
-    if (idx < cin * KK) {
-        const int c = idx / KK, tap = idx % KK;
-        off = (long long)(c / 16) * PER + (c % 16) * KK + tap;
-        valid = true;
-    } else if (idx == cin * KK) {
-        off = 16 * KK;  // bias sum lives in channel group 0
-        valid = true;
-    }
-    const float t = partial_sum(partial, off, (long long)n_cg * PER, G, valid, red);
-    if (slice == 0 && valid) {
-        if (idx < cin * KK) dw[idx] = accumulate ? dw[idx] + t : t;
-        else if (db) db[0] = accumulate ? db[0] + t : t;
-    }
-}
-
 constexpr int IMG_G = 512;
-
-// (csrc/image_bwd.hip: the fused backward of the 16 -> 1 layer leaves its block partials in image_out_wgrad_kernel's layout)
-int image_out_wgrad_reduce3_launch(const float* ws, float* dw, float* db, int cin, int G, int n_cg, int accumulate, hipStream_t st) {
-    const int n = cin * 9 + 1;
-    hipLaunchKernelGGL((image_out_wgrad_reduce<3>), dim3(cdiv(n, 64)), dim3(64 * RED_SLICES), 0, st, ws, dw, db, cin, G, n_cg, accumulate);
-    return check_launch("image_out_wgrad_reduce");
-}
 
 }  // namespace mmif
 
@@ -422,7 +365,7 @@ int image_out_fwd16_launch(const TV& tx, const float* w, const float* bias, floa
     } while (0)
 
 extern "C" size_t mmif_conv2d_image_wgrad_workspace(int32_t c, int32_t ksize) {
-    return (size_t)IMG_G * cdiv(c, 16) * (16 * ksize * ksize + 16) * sizeof(float);
+    return (size_t)IMG_G * cdiv(c, 16) * grouped_per(1, 16, ksize * ksize) * sizeof(float);   // (image_in_wgrad_reduce<ksize>::PER, the larger of the in / out layouts)
 }
 
 extern "C" int mmif_conv2d_image_in_fwd(const float* img, const float* w, const float* bias, const mmif_tensor* y,
@@ -460,10 +403,8 @@ extern "C" int mmif_conv2d_image_in_wgrad(const float* img, const mmif_tensor* g
     DISPATCH_T_KS(gy->dtype, ksize, CALL);
 #undef CALL
     if (int rc = check_launch("image_in_wgrad")) return rc;
-    const int n = cout * ksize * ksize + cout;
-    if (ksize == 3) hipLaunchKernelGGL((image_in_wgrad_reduce<3>), dim3(cdiv(n, 64)), dim3(64 * RED_SLICES), 0, st, ws, dw, db, cout, G, n_og, accumulate);
-    else hipLaunchKernelGGL((image_in_wgrad_reduce<1>), dim3(cdiv(n, 64)), dim3(64 * RED_SLICES), 0, st, ws, dw, db, cout, G, n_og, accumulate);
-    return check_launch("image_in_wgrad_reduce");
+    if (ksize == 3) return wgrad_reduce_launch(image_in_wgrad_reduce<3>{{dw, db, 1, cout, 1, n_og}}, ws, G, accumulate, st);
+    return wgrad_reduce_launch(image_in_wgrad_reduce<1>{{dw, db, 1, cout, 1, n_og}}, ws, G, accumulate, st);
 }
 
 extern "C" int mmif_conv2d_image_out_fwd(const mmif_tensor* x, const float* w, const float* bias, float* img, int32_t cin,
@@ -528,19 +469,11 @@ extern "C" int mmif_conv2d_image_out_wgrad(const mmif_tensor* x, const float* gi
     const int G = (int)(cdiv(npix, 256) < IMG_G ? cdiv(npix, 256) : IMG_G);
     const int n_cg = cdiv(cin, 16);
     hipStream_t st = (hipStream_t)stream;
-    float* ws = defer_ws((float*)workspace, (size_t)G * n_cg * (16 * ksize * ksize + 1) * sizeof(float));
+    float* ws = defer_ws((float*)workspace, (size_t)G * n_cg * grouped_per(16, 1, ksize * ksize) * sizeof(float));      // image_out_wgrad_reduce<ksize>::PER
 #define CALL(T, KS) hipLaunchKernelGGL((image_out_wgrad_kernel<T, KS>), dim3(G, tx.cb), dim3(256), 0, st, tx, gimg, y_img, ws, npix)
     DISPATCH_T_KS(x->dtype, ksize, CALL);
 #undef CALL
     if (int rc = check_launch("image_out_wgrad")) return rc;
-    const int n = cin * ksize * ksize + 1;
-    {
-        RedJob J;
-        J.partial = ws; J.dw = dw; J.db = db; J.type = RED_IMAGE_OUT; J.sl = RED_SLICES; J.G = G; J.accumulate = accumulate;
-        J.p0 = cin; J.p1 = ksize; J.p2 = n_cg; J.p3 = 0; J.nvb = cdiv(n, 64);
-        if (defer_push(J)) return MMIF_OK;
-    }
-    if (ksize == 3) hipLaunchKernelGGL((image_out_wgrad_reduce<3>), dim3(cdiv(n, 64)), dim3(64 * RED_SLICES), 0, st, ws, dw, db, cin, G, n_cg, accumulate);
-    else hipLaunchKernelGGL((image_out_wgrad_reduce<1>), dim3(cdiv(n, 64)), dim3(64 * RED_SLICES), 0, st, ws, dw, db, cin, G, n_cg, accumulate);
-    return check_launch("image_out_wgrad_reduce");
+    if (ksize == 3) return wgrad_reduce_launch(image_out_wgrad_reduce<3>{{dw, db, cin, 1, n_cg, 1}}, ws, G, accumulate, st);
+    return wgrad_reduce_launch(image_out_wgrad_reduce<1>{{dw, db, cin, 1, n_cg, 1}}, ws, G, accumulate, st);
 }

@@ -20,7 +20,7 @@
 // layout, so fragments are fetched with the gfx950 LDS transpose read ds_read_b64_tr_b16
 // (4 pixels x 16 channels per 16-lane group -> per lane 4 consecutive pixels of one channel).
 #include "common.hpp"
-#include "reduce_defer.hpp"
+#include "wgrad_reduce.hpp"
 // the epilogues' 16-byte output stores.  (Round 5 tried them as inline-asm `global_store_dwordx4 ... sc0`, after the sc0 bit had made the
 // streaming encoder's buffer stores 5 % faster: no change in the step once the asm was correct -- a first version without the two wait
 // states a > 8-byte store needs before its data registers are rewritten stored garbage, and the step ran 12 % "faster" on the garbage
@@ -1437,7 +1437,7 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(TV tx, TV tg, float* __
     constexpr int MW = MFW / MGROUPS;                    // M-frags per wave
     constexpr int KSTEPS = 8 / KSPLIT;                   // k-steps per wave per tile
     constexpr int ICW = 16 * ICF;                        // input channels per block
-    constexpr int PER = MFW * 16 * ICW * KK + MFW * 16;  // floats per block partial
+    constexpr int PER = wgrad_mfma_reduce<KS, MFW, ICF>::PER;  // floats per block partial
     constexpr int TILE_BYTES = (2 * ICF * XPL + MFW * 2 * WG_GPL) * 16;
     constexpr int RED_BYTES = PER * 4;
     constexpr int SM_BYTES = TILE_BYTES > RED_BYTES ? TILE_BYTES : RED_BYTES;
@@ -1594,50 +1594,6 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(TV tx, TV tg, float* __
     for (int e = tid; e < PER; e += 256) dst[e] = red[e];
 }
 
-// 64 outputs x 4 G-slices per block: coalesced across outputs, 4-way parallel over G, fixed order
-template <int KS, int MFW, int ICF = 1>
-__global__ __launch_bounds__(256) void wgrad_mfma_reduce(const float* __restrict__ partial, float* __restrict__ dw,
-                                                         float* __restrict__ db, int cin, int cout, int G, int n_icg,
-                                                         int n_ocg, int accumulate) {
-    constexpr int KK = KS * KS, ICW = 16 * ICF;
-    constexpr int PER = MFW * 16 * ICW * KK + MFW * 16;
-    __shared__ float red[4][64];
-    const int total_w = cout * cin * KK;
-    const int o_local = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int idx = blockIdx.x * 64 + o_local;
-    long long off = -1;
-    if (idx < total_w) {
-        const int tap = idx % KK, c = (idx / KK) % cin, o = idx / (KK * cin);
-        const int icg = c / ICW, ic = c % ICW, ocg = o / (MFW * 16), oc = o % (MFW * 16);
-        off = ((long long)icg * n_ocg + ocg) * PER + (oc * ICW + ic) * KK + tap;
-    } else if (idx < total_w + cout) {
-        const int o = idx - total_w;
-        const int ocg = o / (MFW * 16), oc = o % (MFW * 16);
-        off = ((long long)0 * n_ocg + ocg) * PER + MFW * 16 * ICW * KK + oc;
-    }
-    float s = 0.f;
-    if (off >= 0) {
-        const long long stride = (long long)n_icg * n_ocg * PER;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;   // 4 independent chains keep 4+ loads in flight
-        int gi = slice;
-        for (; gi + 12 < G; gi += 16) {
-            s0 += partial[gi * stride + off];
-            s1 += partial[(gi + 4) * stride + off];
-            s2 += partial[(gi + 8) * stride + off];
-            s3 += partial[(gi + 12) * stride + off];
-        }
-        for (; gi < G; gi += 4) s0 += partial[gi * stride + off];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    red[slice][o_local] = s;
-    __syncthreads();
-    if (slice == 0 && off >= 0) {
-        const float t = (red[0][o_local] + red[1][o_local]) + (red[2][o_local] + red[3][o_local]);
-        if (idx < total_w) dw[idx] = accumulate ? dw[idx] + t : t;
-        else if (db != nullptr) db[idx - total_w] = accumulate ? db[idx - total_w] + t : t;
-    }
-}
-
 // ------------------------------------------------------------------ DMA-staged wgrad (3x3, 64 input x 64 output channels per block)
 // Same maths and the same transpose-read fragments as wgrad_mfma_kernel, restructured like conv_dma_kernel: the register-staged
 // kernel above re-stages the 64-channel g tile for every 16 input channels (135 staged bytes per MFMA); here a block owns a
@@ -1654,7 +1610,6 @@ constexpr int WD_GPIECES = (WD_GG + 63) / 64;              // 33
 constexpr int WD_PIECES = WD_XPIECES + WD_GPIECES;         // 74
 constexpr int WD_BUF_BYTES = WD_PIECES * 1024;             // 75776
 constexpr int WDL_ITERS = (WD_PIECES + D_LOAD - 1) / D_LOAD;   // 19 pieces per loader wave per tile
-constexpr int WD_PER = 64 * 64 * 9 + 64;                   // floats per block partial: dW[64 oc][64 ic][9], db[64]
 
 __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV tx, TV tg, float* __restrict__ partial, int tiles_x,
                                                                                int tpi, int total, int G, int n_icg, int n_ocg, SignMap sgn,
@@ -1851,29 +1806,6 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
         }
 }
 
-// dw / db = fixed-order sum of the G block partials of each (icg, ocg) pair
-template <int SL>
-__global__ __launch_bounds__(64 * SL) void wgrad_dma_reduce(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
-                                                        int cin, int cout, int G, int n_icg, int n_ocg, int accumulate) {
-    __shared__ float red[SL][64];
-    const int total_w = cout * cin * 9;
-    const int idx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int npairs = n_icg * n_ocg;
-    long long off = -1;
-    if (idx < total_w) {
-        const int tap = idx % 9, c = (idx / 9) % cin, o = idx / (9 * cin);
-        off = (long long)((c / 64) + n_icg * (o / 64)) * WD_PER + ((o % 64) * 64 + (c % 64)) * 9 + tap;
-    } else if (idx < total_w + cout) {
-        const int o = idx - total_w;
-        off = (long long)(0 + n_icg * (o / 64)) * WD_PER + 64 * 64 * 9 + (o % 64);
-    }
-    const float t = partial_sum<SL>(partial, off, (long long)npairs * WD_PER, G, off >= 0, red);
-    if ((threadIdx.x >> 6) == 0 && off >= 0) {
-        if (idx < total_w) dw[idx] = accumulate ? dw[idx] + t : t;
-        else if (db != nullptr) db[idx - total_w] = accumulate ? db[idx - total_w] + t : t;
-    }
-}
-
 // ------------------------------------------------------------------ host side
 static long long* g_trace = nullptr;  // device buffer [1024][64] for the optional phase trace
 // ------------------------------------------------------------------ fused backward of ONE thin 3x3 layer: dgrad + wgrad ("bwd pair")
@@ -1893,7 +1825,7 @@ __global__ __launch_bounds__(512, NXB == 4 ? 1 : 2) void bwd_pair_kernel(TV tx, 
     constexpr int NCB = 2 * NGB;                          // channel blocks of g = K chunk of the dgrad (<= 4: one chunk)
     constexpr int NKG = 9 * NCB, NKGP = (NKG + 3) / 4 * 4;
     constexpr int WBYTES = NKGP * MF * 256;
-    constexpr int PER = COUT * CIN * 9 + COUT;
+    constexpr int PER = (int)taprow_wgrad_reduce::per(CIN, COUT);
     constexpr int TILE_BYTES = (2 * NXB + NCB) * BP_PL * 16 + WBYTES;
     constexpr int SM_BYTES = TILE_BYTES > PER * 4 ? TILE_BYTES : PER * 4;
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -2134,7 +2066,7 @@ __global__ __launch_bounds__(512, NXB == 4 ? 1 : 2) void bwd_pair_dma_kernel(TV 
     constexpr int NCB = 2 * NGB;
     constexpr int NKG = 9 * NCB, NKGP = (NKG + 3) / 4 * 4;
     constexpr int WBYTES = NKGP * MF * 256;
-    constexpr int PER = COUT * CIN * 9 + COUT;
+    constexpr int PER = (int)taprow_wgrad_reduce::per(CIN, COUT);
     constexpr int NX = 2 * NXB * BP_PL, NT = NX + NCB * BP_PL;   // granules of the x planes / of a whole tile (x planes, then g planes)
     constexpr int NP = (NT + 63) / 64;                            // DMA pieces per tile
     constexpr int BUF_BYTES = NP * 1024;
@@ -2358,20 +2290,19 @@ __global__ __launch_bounds__(512, NXB == 4 ? 1 : 2) void bwd_pair_dma_kernel(TV 
     for (int e = tid; e < PER; e += 512) dst[e] = red[e];
 }
 
-int taprow_reduce_launch(const float* ws, float* dw, float* db, int cin, int cout, int G, int accumulate, hipStream_t st);   // enc_wgrad.hip
 static int num_cus_();
 constexpr int BP_MAXG = 512;
 static int g_bwd_pair_dma = -1;
 void debug_set_bwd_pair_dma(int mode) { g_bwd_pair_dma = mode ? 1 : 0; }
 bool bwd_pair_supported(int ks, int cin, int cout) { return ks == 3 && ((cin == 64 && cout == 32) || (cin == 32 && cout == 16)); }
-size_t bwd_pair_workspace(int cin, int cout) { return (size_t)BP_MAXG * ((size_t)cout * cin * 9 + cout) * sizeof(float); }
+size_t bwd_pair_workspace(int cin, int cout) { return (size_t)BP_MAXG * taprow_wgrad_reduce::per(cin, cout) * sizeof(float); }
 int bwd_pair(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
              hipStream_t st) {
     const int tiles_x = cdiv(tx.w, MT), tiles_y = cdiv(tx.h, MT);
     const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
     const int cap = (cin == 64 ? 1 : 2) * num_cus_();
     const int G = total < cap ? total : (cap < BP_MAXG ? cap : BP_MAXG);
-    ws = defer_ws(ws, (size_t)G * ((size_t)cout * cin * 9 + cout) * sizeof(float));
+    ws = defer_ws(ws, (size_t)G * taprow_wgrad_reduce::per(cin, cout) * sizeof(float));
     // mmif_debug_set_bwd_pair_dma(0): the register-staged kernel (the tests' cross-check; bit-identical results)
     if (g_bwd_pair_dma < 0) g_bwd_pair_dma = 1;
     const bool use_dma = g_bwd_pair_dma == 1 && tg.halo == 1 && tg.folded;
@@ -2386,7 +2317,7 @@ int bwd_pair(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, f
     else
         hipLaunchKernelGGL((bwd_pair_kernel<2, 1>), dim3(G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, tiles_x, tpi, total, G);
     if (int rc = check_launch("bwd_pair")) return rc;
-    return taprow_reduce_launch(ws, dw, db, cin, cout, G, accumulate, st);
+    return wgrad_reduce_launch(taprow_wgrad_reduce{dw, db, cout * cin * 9, cout}, ws, G, accumulate, st);
 }
 
 // ---- backward of a WIDE 3x3 layer (Cin, Cout multiples of 64: decode.0 / decode.1) as one call: wgrad_dma_kernel also leaves the
@@ -2644,7 +2575,7 @@ size_t wgrad_mfma_workspace(int cin, int cout, int ks) {
     const int mfw = pick_mfw(cout), icf = pick_icf(ks, cin, cout);
     size_t a = 0;
     for (int f = 1; f <= icf; f *= 2) {   // (either block width may run)
-        const size_t per = (size_t)mfw * 16 * 16 * f * ks * ks + mfw * 16;
+        const size_t per = grouped_per(16 * f, mfw * 16, ks * ks);      // wgrad_mfma_reduce<ks, mfw, f>::PER
         const size_t b = (size_t)wgrad_G(cin, cout, f) * cdiv(cin, 16 * f) * cdiv(cout, mfw * 16) * per * sizeof(float);
         if (b > a) a = b;
     }
@@ -2666,21 +2597,11 @@ static int launch_wgrad_dma(const TV& tx, const TV& tg, float* dw, float* db, in
     const int n_icg = cdiv(cin, 64), n_ocg = cdiv(cout, 64);
     int G = wgrad_dma_G(cin, cout, g_wgrad_dma_blocks);   // (the workspace is sized for the full grid)
     if (G > total) G = total;   // every tile group owns at least one tile (the reduce sums all G partials)
-    ws = defer_ws(ws, (size_t)G * n_icg * n_ocg * WD_PER * sizeof(float));      // (csrc/reduce_defer.hpp: an arena slot while reductions are deferred)
+    ws = defer_ws(ws, (size_t)G * n_icg * n_ocg * WD_PER * sizeof(float));      // (csrc/wgrad_reduce.hpp: an arena slot while reductions are deferred)
     hipLaunchKernelGGL(wgrad_dma_kernel, dim3(G * n_icg * n_ocg), dim3((D_CONS + D_LOAD) * 64), 0, st, tx, tg, ws, tiles_x, tpi, total, G,
                        n_icg, n_ocg, sgn, g_wgrad_ragged);
     if (int rc = check_launch("wgrad_dma")) return rc;
-    const int n = cout * cin * 9 + cout;
-    const int RG = G;
-    {
-        RedJob J;
-        J.partial = ws; J.dw = dw; J.db = db; J.type = RED_WGRAD_DMA; J.sl = RG > 64 ? 16 : 4; J.G = G; J.accumulate = accumulate;
-        J.p0 = cin; J.p1 = cout; J.p2 = n_icg; J.p3 = n_ocg; J.nvb = cdiv(n, 64);
-        if (defer_push(J)) return MMIF_OK;
-    }
-    if (RG > 64) hipLaunchKernelGGL(wgrad_dma_reduce<16>, dim3(cdiv(n, 64)), dim3(1024), 0, st, ws, dw, db, cin, cout, G, n_icg, n_ocg, accumulate);
-    else hipLaunchKernelGGL(wgrad_dma_reduce<4>, dim3(cdiv(n, 64)), dim3(256), 0, st, ws, dw, db, cin, cout, G, n_icg, n_ocg, accumulate);
-    return check_launch("wgrad_dma_reduce");
+    return wgrad_reduce_launch(wgrad_dma_reduce{{dw, db, cin, cout, n_icg, n_ocg}}, ws, G, accumulate, st);
 }
 
 template <int KS, int MFW, int KSPLIT, int ICF = 1>
@@ -2694,10 +2615,7 @@ static int launch_wgrad_mfma(const TV& tx, const TV& tg, float* dw, float* db, i
     hipLaunchKernelGGL((wgrad_mfma_kernel<KS, MFW, KSPLIT, ICF>), dim3(G * n_icg * n_ocg), dim3(256), 0, st, tx, tg, ws, tiles_x, tpi,
                        total, G, n_icg, n_ocg);
     if (int rc = check_launch("wgrad_mfma")) return rc;
-    const int n = cout * cin * KS * KS + cout;
-    hipLaunchKernelGGL((wgrad_mfma_reduce<KS, MFW, ICF>), dim3(cdiv(n, 64)), dim3(256), 0, st, ws, dw, db, cin, cout, G, n_icg, n_ocg,
-                       accumulate);
-    return check_launch("wgrad_mfma_reduce");
+    return wgrad_reduce_launch(wgrad_mfma_reduce<KS, MFW, ICF>{{dw, db, cin, cout, n_icg, n_ocg}}, ws, G, accumulate, st);
 }
 
 int wgrad_mfma(int ks, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws,

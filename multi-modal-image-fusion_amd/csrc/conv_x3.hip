@@ -27,7 +27,7 @@
 //   pixel-major hi / lo tiles with the LDS transpose read (ds_read_b64_tr_b16), 16 pixels of one tile row per k-step.  It can leave the
 //   ReLU sign map of x for the dgrad that follows (mmif_conv2d_reflect_bwd_wide).
 // wgrad_x3_thin_kernel: the same for <= 48 input / <= 16 output channels: four-wave blocks, 3-5 per CU, 16x16x32 MFMAs.
-#include "common.hpp"
+#include "wgrad_reduce.hpp"
 #include <stdlib.h>
 #include <mutex>
 #include <unordered_map>
@@ -744,7 +744,7 @@ __global__ __launch_bounds__(64 * NWV, 12 / NWV) void wgrad_x3_kernel(TV tx, TV 
                                                      // slower, 0.224 vs 0.188 ms on 16 -> 16: twice the tiles cost more than the second block hides; not instantiated)
     constexpr int PD = KS / 2, TAPS = KS * KS;       // KS = 1: no halo, one tap; the three wave groups v split the k-steps instead of the tap columns
     constexpr int XW_TH = TH, XW_XH = TH + 2 * PD, XW_XW = XW_TW + 2 * PD;
-    constexpr int XW_PER = 64 * 64 * TAPS + 64;      // floats per block partial: dW[64 oc][64 ic][taps], db[64]
+    constexpr int XW_PER = wgrad_x3_reduce::per(TAPS);      // floats per block partial: dW[64 oc][64 ic][taps], db[64]
     constexpr int XW_XPL = XW_XH * XW_XW + (KS == 1 ? 4 : 0);   // 180 / 324 / 132 granules per x plane (= 4 mod 16: the four planes a half wave's transposing
     constexpr int XW_GPL = XW_TH * XW_TW + 4;        // 132 / 260 granules per g plane    read touches fall on disjoint bank quarters)
     constexpr int XW_XG = NXC * XW_XPL, XW_GG = NGC * XW_GPL;      // one precision half of the x / g tile
@@ -1017,7 +1017,6 @@ constexpr int XT_TH = 8, XT_TW = 16, XT_XH = XT_TH + 2, XT_XW = XT_TW + 2;
 constexpr int XT_XPL = XT_XH * XT_XW, XT_GPL = XT_TH * XT_TW + 4;        // 180 / 132 granules per plane: both = 4 mod 16, so that the two planes a 32-lane
                                                                          // group of the transposing read touches fall on disjoint bank halves (184 was 2-way: 35 % extra cycles)
 constexpr int XT_THREADS = 256;
-constexpr int XT_PER = 9 * 3 * 4 * 64 + 64;                            // floats per block partial: [item][u][reg][lane], db[16] (+ pad)
 template <int NXC, bool SIGNS = false>
 __global__ __launch_bounds__(XT_THREADS, 3) void wgrad_x3_thin_kernel(TV tx, TV tg, float* __restrict__ partial, int tiles_x, int tpi, int total,
                                                                       unsigned* __restrict__ signs) {
@@ -1187,7 +1186,6 @@ __global__ __launch_bounds__(XT_THREADS, 3) void wgrad_x3_thin_kernel(TV tx, TV 
 // The three DenseBlock convs of one encoder (16 -> 16, 32 -> 16, 48 -> 16: core/block.py:137-151) in ONE pass over [x0 | x1 | x2] and
 // [g1 | g2 | g3] -- the fp32 form of csrc/enc_wgrad.hip: the same blocks and items as wgrad_x3_thin_kernel, item = (layer L, input block
 // j < L, tap column v), 18 of them; every activation tile is staged once instead of up to three times (0.8 GB per encoder instead of 1.2).
-constexpr int XD_PER = 18 * 768 + 64;                                  // floats per block partial: [item][u][reg][lane], db[3][16] (+ pad)
 __global__ __launch_bounds__(XT_THREADS, 2) void wgrad_x3_dense_kernel(TV tx, TV tg, float* __restrict__ partial, int tiles_x, int tpi, int total) {
     constexpr int NXC = 6;
     constexpr bool SIGNS = false;
@@ -1354,83 +1352,6 @@ __global__ __launch_bounds__(XT_THREADS, 2) void wgrad_x3_dense_kernel(TV tx, TV
         const int L = wave == 0 ? 1 : (wave == 3 ? 2 : 3);
 #pragma unroll
         for (int r = 0; r < 4; ++r) dst[18 * 768 + 16 * (L - 1) + 4 * (lane >> 4) + r] = accb[r];
-    }
-}
-
-__global__ __launch_bounds__(64 * RED_SLICES) void wgrad_x3_dense_reduce(const float* __restrict__ partial, float* __restrict__ dw1, float* __restrict__ db1,
-                                                                        float* __restrict__ dw2, float* __restrict__ db2, float* __restrict__ dw3,
-                                                                        float* __restrict__ db3, int G, int accumulate) {
-    __shared__ float red[RED_SLICES][64];
-    const int e = blockIdx.x * 64 + (threadIdx.x & 63);      // the partial's order
-    float* dst = nullptr;
-    if (e < 18 * 768) {
-        const int ln = e & 63, r = (e >> 6) & 3, u = (e >> 8) % 3, item = e / 768;
-        const int L = item < 3 ? 1 : (item < 9 ? 2 : 3), rel = item - (L == 1 ? 0 : (L == 2 ? 3 : 9));
-        const int j = rel / 3, v = rel - 3 * j;
-        const int o = 4 * (ln >> 4) + r, c = 16 * j + (ln & 15);
-        float* dw = L == 1 ? dw1 : (L == 2 ? dw2 : dw3);
-        dst = dw + ((long long)o * (16 * L) + c) * 9 + u * 3 + v;
-    } else if (e < 18 * 768 + 48) {
-        const int L = (e - 18 * 768) / 16 + 1, o = (e - 18 * 768) % 16;
-        float* db = L == 1 ? db1 : (L == 2 ? db2 : db3);
-        if (db != nullptr) dst = db + o;
-    }
-    const float t = partial_sum(partial, e, XD_PER, G, dst != nullptr, red);
-    if ((threadIdx.x >> 6) == 0 && dst != nullptr) *dst = accumulate ? *dst + t : t;
-}
-
-__global__ __launch_bounds__(64 * RED_SLICES) void wgrad_x3_thin_reduce(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
-                                                                       int cin, int cout, int G, int accumulate) {
-    __shared__ float red[RED_SLICES][64];
-    // the partial's order: [item][u][reg][lane] for the layer's items (all blocks but the last), then db[16] behind all nine (the last block)
-    const int e = (blockIdx.x + 1 < gridDim.x ? blockIdx.x * 64 : 9 * 3 * 4 * 64) + (threadIdx.x & 63);
-    long long dst = -1;
-    if (e < 9 * 3 * 4 * 64) {
-        const int ln = e & 63, r = (e >> 6) & 3, u = (e >> 8) % 3, item = e / 768;
-        const int j = item / 3, v = item - 3 * j;
-        const int o = 4 * (ln >> 4) + r, c = 16 * j + (ln & 15);
-        if (o < cout && c < cin) dst = ((long long)o * cin + c) * 9 + u * 3 + v;
-    } else if (e < 9 * 3 * 4 * 64 + 16) {
-        const int o = e - 9 * 3 * 4 * 64;
-        if (o < cout) dst = -2 - o;
-    }
-    const float t = partial_sum(partial, e, XT_PER, G, dst != -1, red);
-    if ((threadIdx.x >> 6) == 0 && dst != -1) {
-        if (dst >= 0) dw[dst] = accumulate ? dw[dst] + t : t;
-        else if (db != nullptr) { const int o = (int)(-2 - dst); db[o] = accumulate ? db[o] + t : t; }
-    }
-}
-
-// dw / db = fixed-order sum of the G block partials of each (icg, ocg) pair
-template <int SL>
-__global__ __launch_bounds__(64 * SL) void wgrad_x3_reduce(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db,
-                                                       int cin, int cout, int G, int n_icg, int n_ocg, int accumulate, int taps) {
-    // threads walk the PARTIAL's order (register-major tiles: 64 consecutive threads read 64 consecutive floats of every block's partial)
-    // and scatter the one result each to dW's order; walking dW's order instead read 64 different cache lines per load instruction
-    __shared__ float red[SL][64];
-    const int XW_PER = 64 * 64 * taps + 64;
-    const int npairs = n_icg * n_ocg;
-    const long long idx = (long long)blockIdx.x * 64 + (threadIdx.x & 63);      // over npairs x XW_PER
-    const int pair = (int)(idx / XW_PER), e = (int)(idx - (long long)pair * XW_PER);
-    const int icg = pair % n_icg, ocg = pair / n_icg;
-    long long dst = -1;           // index into dw (>= 0), or -2 - o for db[o]
-    if (pair < npairs) {
-        if (e < 64 * 64 * taps) {
-            const int ln = e & 63, r = (e >> 6) & 15, tile = e >> 10;
-            int mt, jt, tap;
-            if (taps == 1) { mt = tile >> 1; jt = tile & 1; tap = 0; }
-            else { const int u = tile % 3, v = (tile / 3) % 3, mj = tile / 9; mt = mj >> 1; jt = mj & 1; tap = u * 3 + v; }
-            const int o = ocg * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5), c = icg * 64 + jt * 32 + (ln & 31);
-            if (o < cout && c < cin) dst = ((long long)o * cin + c) * taps + tap;
-        } else if (icg == 0) {
-            const int o = ocg * 64 + (e - 64 * 64 * taps);
-            if (o < cout) dst = -2 - o;
-        }
-    }
-    const float t = partial_sum<SL>(partial, idx, (long long)npairs * XW_PER, G, dst != -1, red);
-    if ((threadIdx.x >> 6) == 0 && dst != -1) {
-        if (dst >= 0) dw[dst] = accumulate ? dw[dst] + t : t;
-        else if (db != nullptr) { const int o = (int)(-2 - dst); db[o] = accumulate ? db[o] + t : t; }
     }
 }
 
@@ -1621,7 +1542,7 @@ size_t wgrad_x3_workspace(int cin, int cout, int ks) {
         if (G < 1) G = 1;
         const size_t dyn = (size_t)wgrad_x3_G(cin, cout);
         if (dyn > G) G = dyn;
-        return 3 * G * npairs * (64 * 64 + 64) * sizeof(float);
+        return 3 * G * npairs * wgrad_x3_reduce::per(1) * sizeof(float);
     }
     if (ks != 3) return 0;
     const size_t npairs = (size_t)cdiv(cin, 64) * cdiv(cout, 64);
@@ -1629,7 +1550,7 @@ size_t wgrad_x3_workspace(int cin, int cout, int ks) {
     if (G < 1) G = 1;
     const size_t dyn = (size_t)wgrad_x3_G(cin, cout);
     if (dyn > G) G = dyn;
-    return G * npairs * (64 * 64 * 9 + 64) * sizeof(float);
+    return G * npairs * wgrad_x3_reduce::per(9) * sizeof(float);
 }
 
 size_t x3_signs_bytes(int n, int cb, int h, int w) { return (size_t)n * ((cb + 3) / 4) * h * w * 4; }
@@ -1644,11 +1565,7 @@ int wgrad_x3(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout
         if (signs != nullptr) hipLaunchKernelGGL((wgrad_x3_kernel<8, 8, 8, 1, true>), dim3(G * n_icg * n_ocg), dim3(XW_THREADS), 0, st, tx, tg, ws, cin, cout, tiles_x, tpi, total, G, n_icg, n_ocg, signs);
         else hipLaunchKernelGGL((wgrad_x3_kernel<8, 8, 8, 1>), dim3(G * n_icg * n_ocg), dim3(XW_THREADS), 0, st, tx, tg, ws, cin, cout, tiles_x, tpi, total, G, n_icg, n_ocg, signs);
         if (int rc = check_launch("wgrad_x3 1x1")) return rc;
-        const int n = n_icg * n_ocg * (64 * 64 + 64);   // the reduce walks the partial's order
-        const int RG = 3 * G;
-        if (RG > 64) hipLaunchKernelGGL(wgrad_x3_reduce<16>, dim3(cdiv(n, 64)), dim3(1024), 0, st, ws, dw, db, cin, cout, 3 * G, n_icg, n_ocg, accumulate, 1);
-    else hipLaunchKernelGGL(wgrad_x3_reduce<4>, dim3(cdiv(n, 64)), dim3(256), 0, st, ws, dw, db, cin, cout, 3 * G, n_icg, n_ocg, accumulate, 1);
-        return check_launch("wgrad_x3_reduce");
+        return wgrad_reduce_launch(wgrad_x3_reduce{dw, db, cin, cout, n_icg, n_ocg, 1}, ws, 3 * G, accumulate, st);   // (three k-split partials per block)
     }
     const bool thin = cin <= 48 && cout <= 16;
     if (thin) {
@@ -1663,9 +1580,7 @@ int wgrad_x3(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout
             else { if (signs != nullptr) XT_LAUNCH(6, true); else XT_LAUNCH(6); }
 #undef XT_LAUNCH
             if (int rc = check_launch("wgrad_x3 thin")) return rc;
-            const int n = (cin <= 16 ? 3 : (cin <= 32 ? 6 : 9)) * 768;   // the items this layer has (partial order; the bias sums sit behind all nine)
-            hipLaunchKernelGGL(wgrad_x3_thin_reduce, dim3(n / 64 + 1), dim3(64 * RED_SLICES), 0, st, ws, dw, db, cin, cout, G, accumulate);
-            return check_launch("wgrad_x3_thin_reduce");
+            return wgrad_reduce_launch(wgrad_x3_thin_reduce{dw, db, cin, cout}, ws, G, accumulate, st);
         }
     }
     const int th = thin ? 16 : 8;
@@ -1682,11 +1597,7 @@ int wgrad_x3(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout
     else { if (signs != nullptr) XW_LAUNCH(8, 8, 8, 3, true); else XW_LAUNCH(8, 8, 8, 3); }
 #undef XW_LAUNCH
     if (int rc = check_launch("wgrad_x3")) return rc;
-    const int n = n_icg * n_ocg * (64 * 64 * 9 + 64);   // the reduce walks the partial's order
-    const int RG = G;
-    if (RG > 64) hipLaunchKernelGGL(wgrad_x3_reduce<16>, dim3(cdiv(n, 64)), dim3(1024), 0, st, ws, dw, db, cin, cout, G, n_icg, n_ocg, accumulate, 9);
-    else hipLaunchKernelGGL(wgrad_x3_reduce<4>, dim3(cdiv(n, 64)), dim3(256), 0, st, ws, dw, db, cin, cout, G, n_icg, n_ocg, accumulate, 9);
-    return check_launch("wgrad_x3_reduce");
+    return wgrad_reduce_launch(wgrad_x3_reduce{dw, db, cin, cout, n_icg, n_ocg, 9}, ws, G, accumulate, st);
 }
 
 
@@ -1704,8 +1615,7 @@ int wgrad_x3_dense(const TV& tx, const TV& tg, float* dw1, float* db1, float* dw
     if (total < G) G = total;
     hipLaunchKernelGGL(wgrad_x3_dense_kernel, dim3(G), dim3(XT_THREADS), 0, st, tx, tg, ws, tiles_x, tpi, total);
     if (int rc = check_launch("wgrad_x3 dense")) return rc;
-    hipLaunchKernelGGL(wgrad_x3_dense_reduce, dim3((18 * 768 + 64) / 64), dim3(64 * RED_SLICES), 0, st, ws, dw1, db1, dw2, db2, dw3, db3, G, accumulate);
-    return check_launch("wgrad_x3_dense_reduce");
+    return wgrad_reduce_launch(wgrad_x3_dense_reduce{{dw1, dw2, dw3}, {db1, db2, db3}}, ws, G, accumulate, st);
 }
 }  // namespace mmif
 

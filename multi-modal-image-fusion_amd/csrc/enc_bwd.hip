@@ -858,6 +858,5 @@ extern "C" int mmif_dense_encoder_bwd(const mmif_dense_chain* chain_a, const flo
         D[b].dw[0] = d[2]; D[b].db[0] = d[3]; D[b].dw[1] = d[4]; D[b].db[1] = d[5]; D[b].dw[2] = d[6]; D[b].db[2] = d[7];
     }
     if (nb == 2) return enc_wgrad_reduce_pair_launch(A.br[0].partial, D[0], accumulate_a, A.br[1].partial, D[1], accumulate_b, G, st);
-    if (int rc = enc_wgrad_reduce_launch(A.br[0].partial, D[0], G, accumulate_a, st)) return rc;
-    return MMIF_OK;
+    return wgrad_reduce_launch(enc_wgrad_reduce{D[0]}, A.br[0].partial, G, accumulate_a, st);
 }

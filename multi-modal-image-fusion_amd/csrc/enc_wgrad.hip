@@ -14,7 +14,6 @@
 // No K split between waves -> no cross-wave reduction; per-block partials are reduced in a fixed order by a second kernel
 // (deterministic, no atomics).  ~250 B staged per pixel => HBM-bound; 2 blocks per CU (65 KB LDS each).
 #include "enc_wgrad.hpp"
-#include "reduce_defer.hpp"
 
 namespace mmif {
 
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void enc_wgrad_kernel(const float* __restri
 template <int NXB, int NGB>
 __global__ __launch_bounds__(256, 2) void taprow_wgrad_kernel(TV tx, TV tg, float* __restrict__ partial, int tiles_x, int tpi, int total, int G) {
     constexpr int CIN = 16 * NXB, COUT = 16 * NGB;
-    constexpr int PER = COUT * CIN * 9 + COUT;
+    constexpr int PER = (int)taprow_wgrad_reduce::per(CIN, COUT);
     constexpr int TILE_BYTES = (2 * NXB * EW_XPL + 2 * NGB * EW_GPL) * 16;
     constexpr int SM_BYTES = TILE_BYTES > PER * 4 ? TILE_BYTES : PER * 4;
     __shared__ __attribute__((aligned(16))) char smem[SM_BYTES];
@@ -374,36 +373,12 @@ __global__ __launch_bounds__(256, 2) void taprow_wgrad_kernel(TV tx, TV tg, floa
     for (int e = tid; e < PER; e += 256) dst[e] = red[e];
 }
 
-// out[i] = sum_g partial[g][i] (fixed order); the first n_w entries are dW in its natural layout, the rest db
-__global__ __launch_bounds__(64 * RED_SLICES) void taprow_wgrad_reduce(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db, int n_w,
-                                                           int per, int G, int accumulate) {
-    __shared__ float red[RED_SLICES][64];
-    const int idx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const float t = partial_sum(partial, idx, per, G, idx < per, red);
-    if ((threadIdx.x >> 6) != 0 || idx >= per) return;
-    float* p = idx < n_w ? dw + idx : (db != nullptr ? db + (idx - n_w) : nullptr);
-    if (p != nullptr) *p = accumulate ? *p + t : t;
-}
-
 bool wgrad_taprow_supported(int ks, int cin, int cout) {
     if (ks != 3 || cin % 16 || cout % 16) return false;
     const int nxb = cin / 16, ngb = cout / 16;
     return (ngb == 1 && nxb >= 1 && nxb <= 3) || (ngb == 2 && (nxb == 2 || nxb == 4));
 }
-size_t wgrad_taprow_workspace(int cin, int cout) { return (size_t)EW_MAXG * ((size_t)cout * cin * 9 + cout) * sizeof(float); }
-
-// fixed-order reduction of G natural-layout partials ([cout][cin][3][3] then [cout]) -- shared with the fused backward kernel of conv_mfma.hip
-int taprow_reduce_launch(const float* ws, float* dw, float* db, int cin, int cout, int G, int accumulate, hipStream_t st) {
-    const int n_w = cout * cin * 9, per = n_w + cout;
-    {
-        RedJob J;
-        J.partial = ws; J.dw = dw; J.db = db; J.type = RED_TAPROW; J.sl = RED_SLICES; J.G = G; J.accumulate = accumulate;
-        J.p0 = n_w; J.p1 = per; J.p2 = 0; J.p3 = 0; J.nvb = cdiv(per, 64);
-        if (defer_push(J)) return MMIF_OK;
-    }
-    hipLaunchKernelGGL(taprow_wgrad_reduce, dim3(cdiv(per, 64)), dim3(64 * RED_SLICES), 0, st, ws, dw, db, n_w, per, G, accumulate);
-    return check_launch("wgrad_taprow_reduce");
-}
+size_t wgrad_taprow_workspace(int cin, int cout) { return (size_t)EW_MAXG * taprow_wgrad_reduce::per(cin, cout) * sizeof(float); }
 
 int wgrad_taprow(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st) {
     const int tiles_x = cdiv(tx.w, EW_T), tiles_y = cdiv(tx.h, EW_T);
@@ -415,78 +390,18 @@ int wgrad_taprow(const TV& tx, const TV& tg, float* dw, float* db, int cin, int 
     else { if (nxb == 2) GO(2, 2); else GO(4, 2); }
 #undef GO
     if (int rc = check_launch("wgrad_taprow")) return rc;
-    const int n_w = cout * cin * 9, per = n_w + cout;
-    hipLaunchKernelGGL(taprow_wgrad_reduce, dim3(cdiv(per, 64)), dim3(64 * RED_SLICES), 0, st, (const float*)ws, dw, db, n_w, per, G, accumulate);
-    return check_launch("wgrad_taprow_reduce");
+    return wgrad_reduce_launch(taprow_wgrad_reduce{dw, db, cout * cin * 9, cout}, ws, G, accumulate, st);
 }
 
-
-// 64 outputs x 4 slices of the G partials per block; fixed summation order
-__global__ __launch_bounds__(64 * RED_SLICES) void enc_wgrad_reduce(const float* __restrict__ partial, EwDst D, int G, int accumulate) {
-    __shared__ float red[RED_SLICES][64];
-    const int idx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const float t = partial_sum(partial, idx, EW_PER, G, idx < EW_PER, red);
-    if ((threadIdx.x >> 6) != 0 || idx >= EW_PER) return;
-    float* p = nullptr;
-    if (idx < EW_OFF2) p = D.dw[2] + idx;
-    else if (idx < EW_OFF1) p = D.dw[1] + (idx - EW_OFF2);
-    else if (idx < EW_OFF0) p = D.dw[0] + (idx - EW_OFF1);
-    else if (idx < EW_OFFB) {
-        const int oc = (idx - EW_OFF0) >> 4, n = (idx - EW_OFF0) & 15;
-        if (n < 9) p = D.dw0 + oc * 9 + n;
-        else if (n == 9 && D.db0 != nullptr) p = D.db0 + oc;
-    } else {
-        const int L = (idx - EW_OFFB) >> 4, oc = (idx - EW_OFFB) & 15;
-        if (D.db[L] != nullptr) p = D.db[L] + oc;
-    }
-    if (p != nullptr) *p = accumulate ? *p + t : t;
-}
-
-// both branches of a fused encoder backward in ONE launch: blockIdx.y = branch when the destinations differ; a SHARED encoder (the second
-// branch accumulates onto the first's gradients) runs its two sums one after the other in the same blocks -- the order of the two launches
-// this replaces, bit for bit
-struct EwPair { const float* partial[2]; EwDst D[2]; int accumulate[2]; int serial; };
-__global__ __launch_bounds__(64 * RED_SLICES) void enc_wgrad_reduce_pair(EwPair P, int G) {
-    __shared__ float red[RED_SLICES][64];
-    const int idx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int b0 = P.serial ? 0 : blockIdx.y, b1 = P.serial ? 2 : b0 + 1;
-    for (int b = b0; b < b1; ++b) {
-        const float t = partial_sum(P.partial[b], idx, EW_PER, G, idx < EW_PER, red);
-        __syncthreads();      // (red is reused by the second sum)
-        if ((threadIdx.x >> 6) != 0 || idx >= EW_PER) continue;
-        const EwDst& D = P.D[b];
-        float* p = nullptr;
-        if (idx < EW_OFF2) p = D.dw[2] + idx;
-        else if (idx < EW_OFF1) p = D.dw[1] + (idx - EW_OFF2);
-        else if (idx < EW_OFF0) p = D.dw[0] + (idx - EW_OFF1);
-        else if (idx < EW_OFFB) {
-            const int oc = (idx - EW_OFF0) >> 4, n = (idx - EW_OFF0) & 15;
-            if (n < 9) p = D.dw0 + oc * 9 + n;
-            else if (n == 9 && D.db0 != nullptr) p = D.db0 + oc;
-        } else {
-            const int L = (idx - EW_OFFB) >> 4, oc = (idx - EW_OFFB) & 15;
-            if (D.db[L] != nullptr) p = D.db[L] + oc;
-        }
-        if (p != nullptr) *p = P.accumulate[b] ? *p + t : t;
-    }
-}
-
+// both branches of a fused encoder backward in ONE launch (wgrad_reduce_pair, csrc/wgrad_reduce.hpp): in parallel when every destination
+// differs; a SHARED encoder (the second branch accumulates onto the first's gradients) runs its two sums one after the other in the same
+// threads -- the order of the two launches this replaces, bit for bit
 int enc_wgrad_reduce_pair_launch(const float* pa, const EwDst& Da, int acc_a, const float* pb, const EwDst& Db, int acc_b, int G, hipStream_t st) {
-    EwPair P;
-    P.partial[0] = pa; P.partial[1] = pb;
-    P.D[0] = Da; P.D[1] = Db;
-    P.accumulate[0] = acc_a; P.accumulate[1] = acc_b;
-    // any destination in common => the second branch must see the first's result: serial inside the blocks
     bool shared = Da.dw0 == Db.dw0 || (Da.db0 != nullptr && Da.db0 == Db.db0);
     for (int i = 0; i < 3; ++i) shared = shared || Da.dw[i] == Db.dw[i] || (Da.db[i] != nullptr && Da.db[i] == Db.db[i]);
-    P.serial = shared ? 1 : 0;
-    hipLaunchKernelGGL(enc_wgrad_reduce_pair, dim3(cdiv(EW_PER, 64), shared ? 1 : 2), dim3(64 * RED_SLICES), 0, st, P, G);
+    hipLaunchKernelGGL((wgrad_reduce_pair<enc_wgrad_reduce, RED_SLICES>), dim3(cdiv(EW_PER, 64), shared ? 1 : 2), dim3(64 * RED_SLICES), 0, st,
+                       enc_wgrad_reduce{Da}, pa, acc_a, enc_wgrad_reduce{Db}, pb, acc_b, G, shared ? 1 : 0);
     return check_launch("enc_wgrad_reduce_pair");
-}
-
-int enc_wgrad_reduce_launch(const float* partial, const EwDst& D, int G, int accumulate, hipStream_t st) {
-    hipLaunchKernelGGL(enc_wgrad_reduce, dim3(cdiv(EW_PER, 64)), dim3(64 * RED_SLICES), 0, st, partial, D, G, accumulate);
-    return check_launch("enc_wgrad_reduce");
 }
 
 }  // namespace mmif
@@ -515,15 +430,17 @@ extern "C" int mmif_dense_encoder_wgrad(const float* img, const mmif_tensor* x, 
     if (int rc = validate_tensor(x, "x")) return rc;
     if (int rc = validate_tensor(gz, "gz")) return rc;
     MMIF_REQUIRE(img != nullptr && dw0 != nullptr && dw1 != nullptr && dw2 != nullptr && dw3 != nullptr, "dense_encoder_wgrad: NULL image / dW");
-    if (x->dtype == MMIF_F32 && gz->dtype == MMIF_F32) {
+    const bool f32 = x->dtype == MMIF_F32 && gz->dtype == MMIF_F32;
+    MMIF_REQUIRE(f32 || (x->dtype == MMIF_BF16 && gz->dtype == MMIF_BF16), "dense_encoder_wgrad: bf16 tensors expected");
+    MMIF_REQUIRE(x->halo == 0 && x->cb >= 6, "dense_encoder_wgrad: x must be a halo-0 view of >= 6 channel blocks (x0 | x1 | x2)");
+    MMIF_REQUIRE(gz->cb == 8 && (gz->halo == 0 || (gz->flags & MMIF_T_FOLDED)), "dense_encoder_wgrad: gz must be an 8-block view, halo 0 or folded");
+    MMIF_REQUIRE(x->n == gz->n && x->h == gz->h && x->w == gz->w, "dense_encoder_wgrad: x / gz mismatch");
+    if (workspace == nullptr || workspace_bytes < mmif_dense_encoder_wgrad_workspace()) {
+        set_error("dense_encoder_wgrad: workspace too small");
+        return MMIF_EWORKSPACE;
+    }
+    if (f32) {
         // fp32 tensors: the first layer on the image-side kernel, the three DenseBlock convs in ONE split-operand pass (csrc/conv_x3.hip)
-        MMIF_REQUIRE(x->halo == 0 && x->cb >= 6, "dense_encoder_wgrad: x must be a halo-0 view of >= 6 channel blocks (x0 | x1 | x2)");
-        MMIF_REQUIRE(gz->cb == 8 && (gz->halo == 0 || (gz->flags & MMIF_T_FOLDED)), "dense_encoder_wgrad: gz must be an 8-block view, halo 0 or folded");
-        MMIF_REQUIRE(x->n == gz->n && x->h == gz->h && x->w == gz->w, "dense_encoder_wgrad: x / gz mismatch");
-        if (workspace == nullptr || workspace_bytes < mmif_dense_encoder_wgrad_workspace()) {
-            set_error("dense_encoder_wgrad: workspace too small");
-            return MMIF_EWORKSPACE;
-        }
         mmif_tensor g0 = *gz, g123 = *gz;
         g0.cb = 2;
         g123.cb_off = gz->cb_off + 2;
@@ -533,17 +450,9 @@ extern "C" int mmif_dense_encoder_wgrad(const float* img, const mmif_tensor* x, 
         if (int rc = mmif_conv2d_image_in_wgrad(img, &g0, dw0, db0, 16, 3, accumulate, workspace, workspace_bytes, stream)) return rc;
         return wgrad_x3_dense(tx, tg, dw1, db1, dw2, db2, dw3, db3, accumulate, (float*)workspace, (hipStream_t)stream);
     }
-    MMIF_REQUIRE(x->dtype == MMIF_BF16 && gz->dtype == MMIF_BF16, "dense_encoder_wgrad: bf16 tensors expected");
-    MMIF_REQUIRE(x->halo == 0 && x->cb >= 6, "dense_encoder_wgrad: x must be a halo-0 view of >= 6 channel blocks (x0 | x1 | x2)");
-    MMIF_REQUIRE(gz->cb == 8 && (gz->halo == 0 || (gz->flags & MMIF_T_FOLDED)), "dense_encoder_wgrad: gz must be an 8-block view, halo 0 or folded");
-    MMIF_REQUIRE(x->n == gz->n && x->h == gz->h && x->w == gz->w, "dense_encoder_wgrad: x / gz mismatch");
     MMIF_REQUIRE(x->h >= 2 && x->w >= 2, "reflect padding needs h,w >= 2");
     MMIF_REQUIRE((long long)x->cb_total * x->h * x->w < (1ll << 31) && (long long)gz->cb_total * (gz->h + 2) * (gz->w + 2) < (1ll << 31),
                  "dense_encoder_wgrad: one image of x / gz must stay below 2^31 granules (32-bit tile offsets)");
-    if (workspace == nullptr || workspace_bytes < mmif_dense_encoder_wgrad_workspace()) {
-        set_error("dense_encoder_wgrad: workspace too small");
-        return MMIF_EWORKSPACE;
-    }
     TV tx = make_tv(x), tg = make_tv(gz);
     const int tiles_x = cdiv(tx.w, EW_T), tiles_y = cdiv(tx.h, EW_T);
     const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
@@ -551,10 +460,5 @@ extern "C" int mmif_dense_encoder_wgrad(const float* img, const mmif_tensor* x, 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(enc_wgrad_kernel, dim3(G), dim3(256), 0, st, img, tx, tg, (float*)workspace, tiles_x, tpi, total, G);
     if (int rc = check_launch("enc_wgrad")) return rc;
-    EwDst D;
-    D.dw0 = dw0; D.db0 = db0;
-    D.dw[0] = dw1; D.dw[1] = dw2; D.dw[2] = dw3;
-    D.db[0] = db1; D.db[1] = db2; D.db[2] = db3;
-    hipLaunchKernelGGL(enc_wgrad_reduce, dim3(cdiv(EW_PER, 64)), dim3(64 * RED_SLICES), 0, st, (const float*)workspace, D, G, accumulate);
-    return check_launch("enc_wgrad_reduce");
+    return wgrad_reduce_launch(enc_wgrad_reduce{{dw0, db0, {dw1, dw2, dw3}, {db1, db2, db3}}}, (const float*)workspace, G, accumulate, st);
 }

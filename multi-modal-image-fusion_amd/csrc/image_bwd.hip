@@ -17,8 +17,7 @@
 // activation granule and g0 values requested before the current tile's arithmetic (one barrier per tile, double-buffered g0 tile),
 // weight-gradient accumulators in registers over all of a block's tiles, one partial per block reduced in fixed order by
 // image_out_wgrad_reduce (deterministic, no atomics).  HBM-bound by design: 67 MB of activations in, 67 MB of gradient out, 8 MB of image.
-#include "common.hpp"
-#include "reduce_defer.hpp"
+#include "wgrad_reduce.hpp"
 
 namespace mmif {
 
@@ -28,7 +27,6 @@ constexpr int IB_TW = 32, IB_TH = 8;             // output tile: 8 rows x 32 col
 constexpr int IB_GW = IB_TW + 5, IB_GH = IB_TH + 5;
 constexpr int IB_GP = 40;                        // row pitch of the g0 tile in floats (a 32-lane group reads one row: conflict free at any pitch)
 static_assert(IB_GW * IB_GH <= 512, "one g0 value per thread");
-constexpr int IB_PER = 16 * 9 + 1;               // floats per block partial: dW[16][9], db  (image_out_wgrad_reduce<3>'s layout, n_cg = 1)
 
 typedef float f32x2_b __attribute__((ext_vector_type(2)));
 
@@ -254,8 +252,6 @@ __global__ __launch_bounds__(512, 2) void image_out_fwd16_kernel(TV tx, const fl
     }
 }
 
-int image_out_wgrad_reduce3_launch(const float* ws, float* dw, float* db, int cin, int G, int n_cg, int accumulate, hipStream_t st);   // conv_image.hip
-
 }  // namespace mmif
 
 using namespace mmif;
@@ -299,11 +295,5 @@ extern "C" int mmif_conv2d_image_out_bwd(const mmif_tensor* x, const float* gimg
     float* ws = defer_ws((float*)workspace, (size_t)G * IB_PER * sizeof(float));
     hipLaunchKernelGGL(image_out_bwd16_kernel, dim3(G), dim3(512), 0, st, tx, tgx, gimg, y_img, w, ws, tiles_x, tiles_y, (int)total);
     if (int rc = check_launch("image_out_bwd")) return rc;
-    {
-        RedJob J;
-        J.partial = ws; J.dw = dw; J.db = db; J.type = RED_IMAGE_OUT; J.sl = RED_SLICES; J.G = G; J.accumulate = accumulate;
-        J.p0 = cin; J.p1 = ksize; J.p2 = 1; J.p3 = 0; J.nvb = cdiv(cin * 9 + 1, 64);
-        if (defer_push(J)) return MMIF_OK;
-    }
-    return image_out_wgrad_reduce3_launch(ws, dw, db, cin, G, 1, accumulate, st);
+    return wgrad_reduce_launch(image_out_wgrad_reduce<3>{{dw, db, cin, 1, 1, 1}}, ws, G, accumulate, st);   // (the block partials are in image_out_wgrad_kernel's layout, one channel group)
 }

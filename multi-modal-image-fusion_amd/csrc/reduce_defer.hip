@@ -1,38 +1,12 @@
-// Deferred weight-gradient reductions: see reduce_defer.hpp.  The kernel below restates the three reduce kernels' index arithmetic
-// (wgrad_dma_reduce: csrc/conv_mfma.hip, taprow_wgrad_reduce: csrc/enc_wgrad.hip, image_out_wgrad_reduce: csrc/conv_image.hip) around the
-// same partial_sum(): per output the same loads in the same order, so the results are bit-identical to the separate launches.
-#include "reduce_defer.hpp"
+// Deferred weight-gradient reductions: see wgrad_reduce.hpp.  The kernel below takes every queued job's slot from the job's map and its sum
+// from partial_sum(), like the separate launches: per output the same loads in the same order, so the results are bit-identical.
+#include "wgrad_reduce.hpp"
 #include <string.h>
 
 namespace mmif {
 
 constexpr int RD_MAXJOBS = 8;
-constexpr int RD_WD_PER = 64 * 64 * 9 + 64;     // floats of one (input group, output group) partial of wgrad_dma_kernel (WD_PER, csrc/conv_mfma.hip)
 struct RedTable { RedJob j[RD_MAXJOBS]; int start[RD_MAXJOBS + 1]; int n; };
-
-// partial_sum() of common.hpp for a VIRTUAL block: thread vt of 64 * sl threads, its red[sl][64] rows at `red`
-__device__ inline float partial_sum_v(const float* __restrict__ partial, long long off, long long stride, int G, bool valid, int sl, int vt,
-                                      float (*red)[64]) {
-    const int o_local = vt & 63, slice = vt >> 6;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (valid) {
-        int g = slice;
-        for (; g + 3 * sl < G; g += 4 * sl) {
-            s0 += partial[g * stride + off];
-            s1 += partial[(g + sl) * stride + off];
-            s2 += partial[(g + 2 * sl) * stride + off];
-            s3 += partial[(g + 3 * sl) * stride + off];
-        }
-        for (; g < G; g += sl) s0 += partial[g * stride + off];
-    }
-    red[slice][o_local] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    float t = 0.f;
-    if (slice == 0) {
-        for (int q = 0; q < sl; q += 4) t += (red[q][o_local] + red[q + 1][o_local]) + (red[q + 2][o_local] + red[q + 3][o_local]);
-    }
-    return t;
-}
 
 __global__ __launch_bounds__(1024) void reduce_multi_kernel(RedTable T) {
     __shared__ float red[16][64];
@@ -42,45 +16,18 @@ __global__ __launch_bounds__(1024) void reduce_multi_kernel(RedTable T) {
     const int lb = blockIdx.x - T.start[k];
     const int sub = J.sl == 16 ? 0 : threadIdx.x >> 8;              // four 256-thread virtual blocks per launch block when sl == 4
     const int vb = J.sl == 16 ? lb : 4 * lb + sub, vt = J.sl == 16 ? threadIdx.x : (threadIdx.x & 255);
-    const int idx = vb * 64 + (vt & 63);
-    long long off = -1, stride = 0;
-    float* dst = nullptr;
-    if (vb < J.nvb) {
-        if (J.type == RED_WGRAD_DMA) {
-            const int cin = J.p0, cout = J.p1, n_icg = J.p2, n_ocg = J.p3;
-            const int total_w = cout * cin * 9;
-            stride = (long long)(n_icg * n_ocg) * RD_WD_PER;
-            if (idx < total_w) {
-                const int tap = idx % 9, c = (idx / 9) % cin, o = idx / (9 * cin);
-                off = (long long)((c / 64) + n_icg * (o / 64)) * RD_WD_PER + ((o % 64) * 64 + (c % 64)) * 9 + tap;
-                dst = J.dw + idx;
-            } else if (idx < total_w + cout) {
-                const int o = idx - total_w;
-                off = (long long)(0 + n_icg * (o / 64)) * RD_WD_PER + 64 * 64 * 9 + (o % 64);
-                dst = J.db != nullptr ? J.db + o : nullptr;
-            }
-        } else if (J.type == RED_TAPROW) {
-            const int n_w = J.p0, per = J.p1;
-            stride = per;
-            if (idx < per) {
-                off = idx;
-                dst = idx < n_w ? J.dw + idx : (J.db != nullptr ? J.db + (idx - n_w) : nullptr);
-            }
-        } else {
-            const int cin = J.p0, KK = J.p1 * J.p1, n_cg = J.p2, PER = 16 * KK + 1;
-            stride = (long long)n_cg * PER;
-            if (idx < cin * KK) {
-                const int c = idx / KK, tap = idx % KK;
-                off = (long long)(c / 16) * PER + (c % 16) * KK + tap;
-                dst = J.dw + idx;
-            } else if (idx == cin * KK) {
-                off = 16 * KK;      // the bias sum lives in channel group 0
-                dst = J.db;
-            }
+    const int idx = vb < J.nvb ? vb * 64 + (vt & 63) : -1;          // (past the job's last virtual block: no output)
+    RedSlot s = {-1, 0, nullptr};
+    if (idx >= 0) {
+        switch (J.kind) {
+            case RedJob::DMA: s = J.dma.slot(idx); break;
+            case RedJob::TAPROW: s = J.taprow.slot(idx); break;
+            case RedJob::IMAGE_OUT3: s = J.image_out3.slot(idx); break;
+            default: s = J.image_out1.slot(idx); break;
         }
     }
-    const float t = partial_sum_v(J.partial, off < 0 ? 0 : off, stride, J.G, off >= 0, J.sl, vt, red + 4 * sub);
-    if ((vt >> 6) == 0 && off >= 0 && dst != nullptr) *dst = J.accumulate ? *dst + t : t;
+    const float t = partial_sum(J.partial, s.off, s.stride, J.G, J.sl, vt, red + 4 * sub);
+    if ((vt >> 6) == 0 && s.off >= 0 && s.dst != nullptr) *s.dst = J.accumulate ? *s.dst + t : t;
 }
 
 static struct {
