@@ -158,6 +158,16 @@ int mmif_dwconv_dgrad(const float* gy, const float* w, float* dx, int32_t n, int
                       int32_t reflect, void* stream);
 int mmif_dwconv_wgrad(const float* x, const float* gy, float* dw, float* db, int32_t n, int32_t c, int32_t h, int32_t wd,
                       int32_t ksize, int32_t reflect, void* stream);
+/* depth-wise patch conv (groups == channels, kernel == stride == s in [2, 16], padding 0; Attention.pool core/block.py:404-412 and
+ * TransitionBlock(down_mode='stride') :645-654): x, dx [n][c][h][wd]; y, gy [n][c][h / s][wd / s]; w [c][1][s][s]; h, wd >= s.
+ * dgrad writes exactly 0 into the rows and columns beyond floor(h / s) s and floor(wd / s) s.  wgrad runs two stages in a fixed order
+ * (no atomics); db may be NULL. */
+int mmif_patchconv_fwd(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t s,
+                       void* stream);
+int mmif_patchconv_dgrad(const float* gy, const float* w, float* dx, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t s, void* stream);
+size_t mmif_patchconv_wgrad_workspace(int32_t c, int32_t s);
+int mmif_patchconv_wgrad(const float* x, const float* gy, float* dw, float* db, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t s,
+                         void* workspace, size_t workspace_bytes, void* stream);
 /* out = g * [y > 0] on plain fp32 arrays (ReLU backward of the layers above) */
 int mmif_relu_bwd(const float* g, const float* y, float* out, int64_t count, void* stream);
 /* out[c] = sum_{n, pixels} x[n][c][.] (deterministic; the bias gradient of a ConvTranspose2d) */
@@ -332,6 +342,36 @@ int mmif_nonlocal_spatial_fwd(const float* x, float* y, float* l, void* scal, in
                               size_t workspace_bytes, void* stream);
 int mmif_nonlocal_spatial_bwd(const float* x, const float* y, const float* l, const void* scal, const float* g, float* dx, int32_t n, int32_t c,
                               int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Multi-head spatial-reduction self-attention core (Attention.forward of core/block.py:416-431) without the [B, heads, N, M] energy
+ * tensor.  q, o, go, dq: plain NCHW fp32 planes [b][heads * d][n]; k, v, dk, dv: [b][heads * d][m]; head h owns channels h d ... (h + 1) d - 1;
+ *   o[b][h d + c][i] = sum_j softmax_j(scale sum_c' q[b][h d + c'][i] k[b][h d + c'][j]) v[b][h d + c][j],
+ * lse: fp32 [b][heads][n], the log-sum-exp of the scaled logits of every query, written by fwd and read by bwd (which recomputes the
+ * weights from q, k and lse).  m is independent of n.
+ * Limits: d in {8, 16, 32}, heads * d <= 256, b * heads <= 65535, 1 <= n, m < 2^30; anything else returns MMIF_EINVAL (the workspace
+ * query returns 0).  Only bwd needs the workspace.  Results are bit-identical from run to run (no atomics). */
+size_t mmif_sra_workspace(int32_t b, int32_t heads, int32_t d, int64_t n, int64_t m);
+int mmif_sra_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int32_t b, int32_t heads, int32_t d, int64_t n, int64_t m,
+                 float scale, void* stream);
+int mmif_sra_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go, float* dq, float* dk, float* dv,
+                 int32_t b, int32_t heads, int32_t d, int64_t n, int64_t m, float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Glue of the MetaFormer blocks (core/block.py:472-540) on plain NCHW fp32 tensors [n][c][hw].
+ * Channel LayerNorm: per pixel, mean and biased variance over the c <= 256 channels, eps inside the square root, optional weight and
+ * bias [c]; stats: fp32 [n][hw][2] = (mean, 1 / sqrt(var + eps)), written by fwd and read by bwd; dweight / dbias may be NULL.
+ * Residual join: y = act(ls[c] a + rs[c] b), ls / rs optional (NULL = 1), act 0 (none) or 4 (ReLU6); bwd takes the ReLU6 mask from y and
+ * writes da, db and (where asked for) dls[c] = sum gm a, drs[c] = sum gm b.  Channel sums run in two stages over a constant number of
+ * chunks, in a fixed order; their partials live in a workspace of mmif_glue_workspace(c) bytes (not needed when no sum is asked for:
+ * layernorm_bwd without dweight and dbias, join_bwd without ls and rs). */
+size_t mmif_glue_workspace(int32_t c);
+int mmif_layernorm_fwd(const float* x, const float* weight, const float* bias, float* y, float* stats, int32_t n, int32_t c, int64_t hw, float eps,
+                       void* stream);
+int mmif_layernorm_bwd(const float* x, const float* gy, const float* weight, const float* stats, float* dx, float* dweight, float* dbias, int32_t n,
+                       int32_t c, int64_t hw, void* workspace, size_t workspace_bytes, void* stream);
+int mmif_join_fwd(const float* a, const float* b, const float* ls, const float* rs, float* y, int32_t n, int32_t c, int64_t hw, int32_t act,
+                  void* stream);
+int mmif_join_bwd(const float* a, const float* b, const float* ls, const float* rs, const float* y, const float* gy, float* da, float* db, float* dls,
+                  float* drs, int32_t n, int32_t c, int64_t hw, int32_t act, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- PFNetv2's self-learned fusion (core/model.py:120-124,134-141): the conv stack ConvLayer(2,2) -> ConvLayer(2,2) ->
  *      ConvLayer(2,1,act=None) applied to every channel pair (feat1[:,i], feat2[:,i]) with SHARED weights.  One "pair conv"

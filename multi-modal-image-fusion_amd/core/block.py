@@ -1,11 +1,13 @@
 # -*- coding: utf-8 -*-
 """Network blocks -- API mirror of the reference's core/block.py for the hot-path blocks
-(ConvLayer :26-118, DenseBlock :137-151, ConvBlock :708-722, RFN :737-759, NestDecoder :836-867,
+(ConvLayer :26-118, DenseBlock :137-151, Attention :355-434, MetaFormerBlock and its sub-classes :503-617, ConvBlock :708-722, RFN :737-759, NestDecoder :836-867,
 Upsample/Downsample :941-991), executed by hand-written HIP kernels.
 
 Called standalone (NCHW tensors in / out) every block converts at its boundary; inside the models
 (core/model.py) the whole network runs on blocked-NHWC buffers without these conversions.
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -17,8 +19,9 @@ from mmif.tensor import BT
 
 from .fusion import concat_fusion, element_fusion
 
-__all__ = ['ConvLayer', 'ResBlock', 'DenseBlock', 'SepConvBlock', 'Res2ConvBlock', 'ConvBlock', 'ECB', 'DCB', 'RFN', 'NestEncoder', 'NestDecoder', 'FSDecoder', 'Downsample',
-           'Upsample', 'MaxPool2d']
+__all__ = ['ConvLayer', 'ResBlock', 'DenseBlock', 'SepConvBlock', 'Res2ConvBlock', 'Attention', 'FFN', 'Scale', 'LayerNorm', 'BatchNorm2d', 'MetaFormerBlock',
+           'ConvFormerBlock', 'Res2FormerBlock', 'TransformerBlock', 'TransitionBlock', 'ConvBlock', 'ECB', 'DCB', 'RFN', 'NestEncoder', 'NestDecoder', 'FSDecoder',
+           'Downsample', 'Upsample', 'MaxPool2d']
 
 
 class _ConvLayerFn(torch.autograd.Function):
@@ -176,6 +179,26 @@ class _DwConvFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _PatchConvFn(torch.autograd.Function):
+    """depth-wise nn.Conv2d with kernel == stride in 2..16 and padding 0 (groups == channels) on csrc/conv_general.hip -- Attention.pool,
+    TransitionBlock(down_mode='stride')"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        T.require_device(x, "ConvLayer input")
+        xd, wd = x.detach().contiguous().float(), weight.detach().contiguous().float()
+        ctx.saved, ctx.has_bias = (xd, wd), bias is not None
+        return T.patchconv_fwd(xd, wd, bias.detach().contiguous().float() if bias is not None else None)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xd, wd = ctx.saved
+        gy = gy.contiguous().float()
+        dw, db = T.patchconv_wgrad(xd, gy, wd.shape[2], ctx.has_bias)
+        dx = T.patchconv_dgrad(gy, wd, tuple(xd.shape[2:])) if ctx.needs_input_grad[0] else None
+        return dx, dw, db
+
+
 class _NormActFn(torch.autograd.Function):
     """norm + activation epilogue of a ConvLayer (reference core/block.py:78-92) on the HIP kernels (csrc/norm.hip):
     nn.BatchNorm2d (batch statistics + running-buffer update when training, running buffers in eval) or nn.GroupNorm(c, c),
@@ -271,10 +294,12 @@ class ConvLayer(nn.Module):
         # the HIP kernels cover exactly what the hot-path models use
         # what follows the conv: nothing / ReLU fused into the conv kernels, or a norm (+ act) / other activation epilogue kernel
         depthwise = groups > 1 and groups == in_ch == out_ch and layer is nn.Conv2d and stride == 1 and ksize in (1, 3) and padding == ksize // 2
+        # depth-wise patch conv: kernel == stride, no padding (Attention.pool, TransitionBlock(down_mode='stride'))
+        patch = groups > 1 and groups == in_ch == out_ch and layer is nn.Conv2d and ksize == stride and 2 <= ksize <= 16 and padding == 0
         epi_ok = (pre_norm is None and norm in (None, nn.BatchNorm2d, nn.GroupNorm) and act in _ACT_CODE and dilation == 1
-                  and (groups == 1 or depthwise))
-        self._epilogue = epi_ok and (norm is not None or act in (nn.LeakyReLU, nn.Tanh, nn.ReLU6) or depthwise)
-        self._depthwise = depthwise
+                  and (groups == 1 or depthwise or patch))
+        self._epilogue = epi_ok and (norm is not None or act in (nn.LeakyReLU, nn.Tanh, nn.ReLU6) or depthwise or patch)
+        self._depthwise, self._patch = depthwise, patch
         plain = epi_ok and not self._epilogue
         geom_hot = (layer is nn.Conv2d and stride == 1 and ksize in (1, 3) and padding == ksize // 2 and not depthwise
                     and (padding_mode == 'reflect' or ksize == 1) and bias
@@ -286,7 +311,7 @@ class ConvLayer(nn.Module):
         self._hip = plain and geom_hot                       # hot-path kernels, ReLU fused
         self._gen = plain and not geom_hot and geom_gen      # general kernels, ReLU fused
         self._conv_hot = geom_hot                            # (which conv kernels an epilogue layer uses)
-        self._epilogue = self._epilogue and (geom_hot or geom_gen or depthwise)
+        self._epilogue = self._epilogue and (geom_hot or geom_gen or depthwise or patch)
         self._geom = (stride, padding, padding_mode == 'reflect' and padding > 0)
         self._init_weights()
 
@@ -294,6 +319,8 @@ class ConvLayer(nn.Module):
         conv = self.layers[0]
         if self._depthwise:
             return _DwConvFn.apply(x, conv.weight, conv.bias, self._geom[2])
+        if self._patch:
+            return _PatchConvFn.apply(x, conv.weight, conv.bias)
         if self._conv_hot:
             return _ConvLayerFn.apply(x, conv.weight, conv.bias, relu)
         stride, padding, reflect = self._geom
@@ -397,6 +424,261 @@ class Res2ConvBlock(SepConvBlock):
             y = self.dwconvs[i](y)
             outs.append(y)
         return concat_fusion(outs)
+
+
+class _SraFn(torch.autograd.Function):
+    """the attention core softmax_M(scale q^T k) v per head on csrc/attention.hip: q [B, A, N], k, v [B, A, M] -> o [B, A, N] in the
+    layout the projection reads.  Saved for backward: q, k, v, o and one log-sum-exp per (sample, head, query); the weights are
+    recomputed tile by tile in both directions, so nothing of size N x M exists."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale):
+        q, k, v = (t.detach().contiguous() for t in (q, k, v))
+        o, lse = T.sra_fwd(q, k, v, heads, scale)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.meta = (heads, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, o, lse = ctx.saved_tensors
+        dq, dk, dv = T.sra_bwd(q, k, v, o, lse, go.contiguous(), *ctx.meta)
+        return dq, dk, dv, None, None
+
+
+def _sra_impl():
+    """$MMIF_SRA = hip (default) | torch: the streaming kernels, or the stock fp32 composition everywhere (A/B comparison, tolerance yardstick)"""
+    v = os.environ.get("MMIF_SRA", "hip")
+    if v not in ("hip", "torch"):
+        raise ValueError(f"MMIF_SRA must be 'hip' or 'torch', got {v!r}")
+    return v
+
+
+def _sra_torch(q, k, v, heads, scale):
+    """the stock composition of reference core/block.py:419-431 on the same [B, A, N] / [B, A, M] planes (energy tensor [B, heads, N, M])"""
+    b, a, n = q.shape
+    d = a // heads
+    attn = (q.reshape(b, heads, d, n).transpose(2, 3) @ k.reshape(b, heads, d, -1)) * scale
+    return (attn.softmax(dim=-1) @ v.reshape(b, heads, d, -1).transpose(2, 3)).transpose(2, 3).reshape(b, a, n)
+
+
+def sra_core(q, k, v, heads, scale):
+    """o[b][h d + c][i] = sum_j softmax_j(scale q_i . k_j)[h] v[b][h d + c][j] for q [B, A, N], k, v [B, A, M], A = heads * d.
+    GPU fp32 operands with d in {8, 16, 32} and A <= 256 run on the HIP kernels; anything else (and $MMIF_SRA=torch) is the stock composition."""
+    if _sra_impl() == 'hip' and T.sra_supported(q, k, v, heads):
+        return _SraFn.apply(q, k, v, heads, scale)
+    return _sra_torch(q, k, v, heads, scale)
+
+
+class Attention(nn.Module):
+    """reference core/block.py:355-434: multi-head self-attention whose keys and values come from a spatially reduced copy of the
+    input (depth-wise kernel = stride = sr_ratio conv, or average pooling).  q / k / v / proj are ConvLayers; the core runs on
+    csrc/attention.hip and writes [B, att_dim, H*W] directly, so no permute is left between it and the projection."""
+
+    def __init__(self, in_ch, out_ch, num_heads=None, qkv_bias=False, proj_bias=False, norm=None, act=None, sr_ratio=None, down_mode='stride'):
+        super(Attention, self).__init__()
+        self.in_ch, self.out_ch = in_ch, out_ch
+        self.num_heads = num_heads if num_heads else in_ch // 16
+        self.head_dim = in_ch // self.num_heads
+        self.att_dim = self.num_heads * self.head_dim
+        self.scale = self.head_dim**-0.5
+        self.q = ConvLayer(in_ch, self.att_dim, ksize=1, bias=qkv_bias, norm=norm, act=act)
+        self.k = ConvLayer(in_ch, self.att_dim, ksize=1, bias=qkv_bias, norm=norm, act=act)
+        self.v = ConvLayer(in_ch, self.att_dim, ksize=1, bias=qkv_bias, norm=norm, act=act)
+        self.proj = ConvLayer(self.att_dim, out_ch, ksize=1, bias=proj_bias, norm=norm, act=act)
+        self.sr_ratio = sr_ratio if sr_ratio else 16 // (in_ch // 16)
+        if down_mode == 'stride':
+            self.pool = ConvLayer(in_ch, in_ch, ksize=self.sr_ratio, stride=self.sr_ratio, padding=0, groups=in_ch, bias=False, norm=norm, act=act)
+        elif down_mode == 'avgpool':
+            self.pool = nn.AvgPool2d(self.sr_ratio, self.sr_ratio)
+
+    def forward(self, x):
+        b, _, h, w = x.shape
+        q = self.q(x).flatten(2)
+        x_pool = self.pool(x) if self.sr_ratio > 1 else x
+        k, v = self.k(x_pool).flatten(2), self.v(x_pool).flatten(2)
+        out = sra_core(q, k, v, self.num_heads, self.scale).reshape(b, self.att_dim, h, w)
+        return self.proj(out)
+
+
+class FFN(nn.Module):
+    """reference core/block.py:437-457: point-wise expand -> depth-wise 3 x 3 -> point-wise project"""
+
+    def __init__(self, num_ch, scale=4, bias=False, norm=None, act=nn.ReLU6):
+        super(FFN, self).__init__()
+        self.num_ch, self.scale = num_ch, scale
+        hid_ch = num_ch * scale
+        self.layers = nn.Sequential(ConvLayer(num_ch, hid_ch, ksize=1, bias=bias, norm=norm, act=act),
+                                    ConvLayer(hid_ch, hid_ch, ksize=3, groups=hid_ch, bias=bias, norm=norm, act=act),
+                                    ConvLayer(hid_ch, num_ch, ksize=1, bias=bias, norm=norm, act=None))
+
+    def forward(self, x):
+        return self.layers(x)
+
+
+class Scale(nn.Module):
+    """reference core/block.py:460-469: one learnable factor per channel"""
+
+    def __init__(self, num_ch, init_value=1.0, trainable=True):
+        super(Scale, self).__init__()
+        self.num_ch, self.init_value = num_ch, init_value
+        self.scale = nn.Parameter(init_value * torch.ones(num_ch), requires_grad=trainable)
+
+    def forward(self, x):
+        return self.scale.unsqueeze(-1).unsqueeze(-1) * x
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """channel LayerNorm on csrc/glue.hip; saved for backward: x and the per-pixel (mean, 1 / sqrt(var + eps))"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        T.require_device(x, "LayerNorm input")
+        xd = x.detach().contiguous()
+        wd = weight.detach().reshape(-1).contiguous() if weight is not None else None
+        bd = bias.detach().reshape(-1).contiguous() if bias is not None else None
+        y, stats = T.layernorm_fwd(xd, wd, bd, eps)
+        ctx.saved = (xd, wd, stats)
+        ctx.meta = (weight is not None, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xd, wd, stats = ctx.saved
+        has_w, has_b = ctx.meta
+        dx, dw, db = T.layernorm_bwd(xd, gy.contiguous().float(), wd, stats, has_w, has_b)
+        return dx, (dw.reshape(-1, 1, 1) if has_w else None), (db.reshape(-1, 1, 1) if has_b else None), None
+
+
+class _JoinFn(torch.autograd.Function):
+    """the residual join y = act(ls[c] a + rs[c] b) of MetaFormerBlock.forward (csrc/glue.hip): one launch forward, one grid-wide launch
+    backward plus the fixed-order sum of dls / drs where there are Scale parameters; ls / rs are those parameters or None; act is
+    ACT_NONE or ACT_RELU6"""
+
+    @staticmethod
+    def forward(ctx, a, b, ls, rs, act):
+        T.require_device(a, "MetaFormerBlock input")
+        ad, bd = a.detach().contiguous().float(), b.detach().contiguous().float()
+        lsd = ls.detach().contiguous() if ls is not None else None
+        rsd = rs.detach().contiguous() if rs is not None else None
+        y = T.join_fwd(ad, bd, lsd, rsd, act)
+        ctx.saved, ctx.act = (ad, bd, lsd, rsd, y), act
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        ad, bd, lsd, rsd, y = ctx.saved
+        da, db, dls, drs = T.join_bwd(ad, bd, lsd, rsd, y, gy.contiguous().float(), ctx.act)
+        return da, db, dls, drs, None
+
+
+class LayerNorm(nn.Module):
+    """reference core/block.py:472-500: mean / biased variance over `normalized_dim`, eps inside the square root, optional
+    weight and bias of shape [C, 1, 1].  normalized_dim == (1,) on a 4-D GPU tensor with C <= 256 runs on csrc/glue.hip; other
+    settings are the tensor-level composition."""
+
+    def __init__(self, affine_shape=None, normalized_dim=(1, ), scale=True, bias=False, eps=1e-6):
+        super(LayerNorm, self).__init__()
+        self.normalized_dim, self.use_scale, self.use_bias = normalized_dim, scale, bias
+        self.weight = nn.Parameter(torch.ones((affine_shape, 1, 1))) if scale else None
+        self.bias = nn.Parameter(torch.zeros((affine_shape, 1, 1))) if bias else None
+        self.eps = eps
+
+    def forward(self, x):
+        if (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and tuple(self.normalized_dim) == (1, ) and x.shape[1] <= T.LAYERNORM_MAX_C
+                and all(p is None or p.numel() == x.shape[1] for p in (self.weight, self.bias))):
+            return _LayerNormFn.apply(x, self.weight if self.use_scale else None, self.bias if self.use_bias else None, self.eps)
+        c = x - x.mean(self.normalized_dim, keepdim=True)
+        s = c.pow(2).mean(self.normalized_dim, keepdim=True)
+        x = c / torch.sqrt(s + self.eps)
+        if self.use_scale:
+            x = x * self.weight
+        if self.use_bias:
+            x = x + self.bias
+        return x
+
+
+class BatchNorm2d(nn.BatchNorm2d):
+    """nn.BatchNorm2d whose forward runs on the norm kernels (csrc/norm.hip, no activation) for 4-D GPU inputs with affine parameters
+    of dtype float32 -- batch statistics and the running-buffer update when training, SyncBN statistics when mmif.dist has them on; anything else is
+    the stock module.  Same parameters and buffers, so `norm1.*` / `norm2.*` state_dict keys are the reference's."""
+
+    def forward(self, x):
+        if x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and self.affine:
+            return _NormActFn.apply(x, self.weight, self.bias, self, T.ACT_NONE)
+        return super(BatchNorm2d, self).forward(x)
+
+
+class MetaFormerBlock(nn.Module):
+    """reference core/block.py:503-540: x -> act(ls1 * mixer(norm1(x)) + rs1 * x) -> act(ls2 * ffn(norm2(.)) + rs2 * .);
+    norm_layer=nn.BatchNorm2d maps to the BatchNorm2d above"""
+
+    def __init__(self, in_ch, out_ch, token_mixer=nn.Identity, norm_layer=LayerNorm, act_layer=nn.Identity, layer_scale=None, res_scale=None):
+        super(MetaFormerBlock, self).__init__()
+        self.in_ch, self.out_ch = in_ch, out_ch
+        if norm_layer is nn.BatchNorm2d:
+            norm_layer = BatchNorm2d
+        self.norm1 = norm_layer(in_ch)
+        self.token_mixer = token_mixer(in_ch, out_ch)
+        self.layer_scale1 = Scale(out_ch, layer_scale) if layer_scale else nn.Identity()
+        self.res_scale1 = Scale(out_ch, res_scale) if res_scale else nn.Identity()
+        self.norm2 = norm_layer(out_ch)
+        self.ffn = FFN(out_ch)
+        self.layer_scale2 = Scale(out_ch, layer_scale) if layer_scale else nn.Identity()
+        self.res_scale2 = Scale(out_ch, res_scale) if res_scale else nn.Identity()
+        self.act = act_layer()
+        self._act_code = _ACT_CODE.get(act_layer)
+
+    def _join(self, a, b, ls, rs):
+        act = T.ACT_NONE if isinstance(self.act, nn.Identity) else self._act_code
+        if (a.is_cuda and a.dim() == 4 and a.shape == b.shape and a.dtype == b.dtype == torch.float32 and act in (T.ACT_NONE, T.ACT_RELU6)
+                and all(isinstance(m, (Scale, nn.Identity)) for m in (ls, rs))):
+            return _JoinFn.apply(a, b, ls.scale if isinstance(ls, Scale) else None, rs.scale if isinstance(rs, Scale) else None, act)
+        return self.act(ls(a) + rs(b))   # CPU tensors, other activations: the stock composition
+
+    def forward(self, x):
+        out = self._join(self.token_mixer(self.norm1(x)), x, self.layer_scale1, self.res_scale1)
+        return self._join(self.ffn(self.norm2(out)), out, self.layer_scale2, self.res_scale2)
+
+
+class ConvFormerBlock(MetaFormerBlock):
+    """reference core/block.py:543-560"""
+
+    def __init__(self, in_ch, out_ch, norm_layer=nn.BatchNorm2d, act_layer=nn.ReLU6, layer_scale=None, res_scale=None):
+        super(ConvFormerBlock, self).__init__(in_ch, out_ch, norm_layer=norm_layer, act_layer=act_layer, layer_scale=layer_scale, res_scale=res_scale)
+        self.token_mixer = SepConvBlock(in_ch, out_ch, residual=True, attention=False)
+
+
+class Res2FormerBlock(MetaFormerBlock):
+    """reference core/block.py:583-600"""
+
+    def __init__(self, in_ch, out_ch, norm_layer=nn.BatchNorm2d, act_layer=nn.ReLU6, layer_scale=None, res_scale=None):
+        super(Res2FormerBlock, self).__init__(in_ch, out_ch, norm_layer=norm_layer, act_layer=act_layer, layer_scale=layer_scale, res_scale=res_scale)
+        self.token_mixer = Res2ConvBlock(in_ch, out_ch, residual=True, attention=False)
+
+
+class TransformerBlock(MetaFormerBlock):
+    """reference core/block.py:603-617"""
+
+    def __init__(self, in_ch, out_ch, norm_layer=nn.BatchNorm2d, act_layer=nn.ReLU6, layer_scale=None, res_scale=None):
+        super(TransformerBlock, self).__init__(in_ch, out_ch, norm_layer=norm_layer, act_layer=act_layer, layer_scale=layer_scale, res_scale=res_scale)
+        self.token_mixer = Attention(in_ch, out_ch)
+
+
+class TransitionBlock(nn.Module):
+    """reference core/block.py:620-664: down-sampling (max-pool, or depth-wise kernel = stride conv) followed by a point-wise ConvLayer"""
+
+    def __init__(self, in_ch, out_ch, stride=2, bias=False, norm=None, act=nn.ReLU6, down_mode='stride'):
+        super(TransitionBlock, self).__init__()
+        self.in_ch, self.out_ch = in_ch, out_ch
+        if down_mode == 'maxpool':
+            self.layers = nn.Sequential(MaxPool2d(stride, stride), ConvLayer(in_ch, out_ch, ksize=1, bias=bias, norm=norm, act=act))
+        elif down_mode == 'stride':
+            self.layers = nn.Sequential(ConvLayer(in_ch, in_ch, ksize=stride, stride=stride, padding=0, groups=in_ch, bias=bias, norm=norm, act=act),
+                                        ConvLayer(in_ch, out_ch, ksize=1, bias=bias, norm=norm, act=act))
+
+    def forward(self, x):
+        return self.layers(x)
 
 
 class DenseBlock(nn.Module):

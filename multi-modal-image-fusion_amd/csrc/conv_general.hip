@@ -368,6 +368,98 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restri
     if (threadIdx.x == 0 && db != nullptr) db[ch] = s;
 }
 
+// ------------------------------------------------------------------ depth-wise patch conv (groups == channels, kernel == stride == s in 2..16, padding 0)
+// (Attention.pool, reference core/block.py:404-412, and TransitionBlock(down_mode='stride') :645-654): every output reads its own s x s patch
+constexpr int PC_MAXS = 16;
+constexpr int PC_CHUNKS = 64;   // the weight gradient splits the (sample, output row) pairs into this many chunks (a constant: results do not depend on the device)
+
+// L = the largest power of two <= min(64, s s) lanes share an output: lane l takes taps l, l + L, ... (neighbouring lanes read neighbouring
+// columns of a patch row), then a butterfly over the L lanes adds them in a fixed order
+__global__ __launch_bounds__(256) void patchconv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ y, long long planes, int c, int h, int wd, int s, int L) {
+    const int oh = h / s, ow = wd / s, ss = s * s;
+    const long long total = planes * oh * ow;
+    const int l = threadIdx.x & (L - 1);
+    const long long per = 256 / L;
+    for (long long i0 = (long long)blockIdx.x * per; i0 < total; i0 += (long long)gridDim.x * per) {   // (uniform trip count: every lane reaches the shuffles)
+        const long long i = i0 + threadIdx.x / L;
+        float r = 0.f;
+        if (i < total) {
+            const int ox = (int)(i % ow), oy = (int)((i / ow) % oh);
+            const long long plane = i / ((long long)oh * ow);
+            const float* pl = x + plane * h * wd + (long long)oy * s * wd + ox * s;
+            const float* wc = w + (plane % c) * ss;
+            for (int t = l; t < ss; t += L) {
+                const int u = t / s;
+                r = fmaf(wc[t], pl[(long long)u * wd + (t - u * s)], r);
+            }
+        }
+        for (int o = L >> 1; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+        if (i < total && l == 0) y[i] = r + (bias != nullptr ? bias[(int)((i / ((long long)oh * ow)) % c)] : 0.f);
+    }
+}
+
+// dx[y][x] = w[y % s][x % s] g[y / s][x / s] inside the covered area, exactly 0 in the rows and columns beyond floor(h / s) s, floor(w / s) s
+__global__ void patchconv_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ w, float* __restrict__ dx, long long planes, int c, int h,
+                                       int wd, int s) {
+    const int oh = h / s, ow = wd / s, ss = s * s;
+    const long long total = planes * h * wd;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % wd), y = (int)((i / wd) % h);
+        const long long plane = i / ((long long)h * wd);
+        const int oy = y / s, ox = x / s;
+        float r = 0.f;
+        if (oy < oh && ox < ow) r = w[(plane % c) * ss + (y - oy * s) * s + (x - ox * s)] * g[(plane * oh + oy) * ow + ox];
+        dx[i] = r;
+    }
+}
+
+// stage 1: block (channel, chunk) -> partial[chunk][channel][s s + 1] (the last word: the bias gradient).  Thread = (lane, tap): a lane walks
+// every lanes-th output of the chunk in order, then thread (0, tap) adds the lanes in order.
+__global__ __launch_bounds__(256) void patchconv_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ partial, int n,
+                                                              int c, int h, int wd, int s, long long rows_per_chunk) {
+    __shared__ float sm[256], smb[256];
+    const int oh = h / s, ow = wd / s, ss = s * s, lanes = 256 / ss;
+    const int ch = blockIdx.x, chunk = blockIdx.y;
+    const int tap = threadIdx.x % ss, lane = threadIdx.x / ss, u = tap / s, v = tap - u * s;
+    const long long rows = (long long)n * oh, r0 = chunk * rows_per_chunk, r1 = r0 + rows_per_chunk < rows ? r0 + rows_per_chunk : rows;
+    float acc = 0.f, accb = 0.f;
+    if (lane < lanes && r0 < r1) {
+        for (long long e = r0 * ow + lane; e < r1 * ow; e += lanes) {
+            const long long row = e / ow;
+            const int ox = (int)(e - row * ow), in_ = (int)(row / oh), oy = (int)(row - (long long)in_ * oh);
+            const long long plane = (long long)in_ * c + ch;
+            const float gv = g[(plane * oh + oy) * ow + ox];
+            acc = fmaf(gv, x[plane * h * wd + ((long long)oy * s + u) * wd + ox * s + v], acc);
+            accb += gv;
+        }
+    }
+    sm[threadIdx.x] = acc;
+    smb[threadIdx.x] = accb;
+    __syncthreads();
+    if (lane == 0) {
+        float t = 0.f, tb = 0.f;
+        for (int l = 0; l < lanes; ++l) {
+            t += sm[l * ss + tap];
+            tb += smb[l * ss + tap];
+        }
+        float* out = partial + ((long long)chunk * c + ch) * (ss + 1);
+        out[tap] = t;
+        if (tap == 0) out[ss] = tb;
+    }
+}
+
+// stage 2: dw[c][tap], db[c] = sum of the chunk partials, in chunk order
+__global__ void patchconv_wgrad_reduce(const float* __restrict__ partial, float* __restrict__ dw, float* __restrict__ db, int c, int ss, int chunks) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= c * (ss + 1)) return;
+    const int ch = idx / (ss + 1), t = idx - ch * (ss + 1);
+    float a = 0.f;
+    for (int k = 0; k < chunks; ++k) a += partial[((long long)k * c + ch) * (ss + 1) + t];
+    if (t < ss) dw[ch * ss + t] = a;
+    else if (db != nullptr) db[ch] = a;
+}
+
 static int grid1d(long long total) {
     long long b = (total + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 65535 * 16 ? 65535 * 16 : b));
@@ -550,4 +642,55 @@ extern "C" int mmif_dwconv_wgrad(const float* x, const float* gy, float* dw, flo
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "dwconv_wgrad: ksize must be 1 or 3 (got %d)", ksize);
     hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3(c), dim3(256), 0, (hipStream_t)stream, x, gy, dw, db, n, c, h, wd, ksize, reflect);
     return check_launch("dwconv_wgrad");
+}
+
+// ---- depth-wise patch conv (groups == channels, kernel == stride == s, padding 0): x, dx [n][c][h][w]; y, gy [n][c][h / s][w / s]; w [c][1][s][s] ----
+static int check_pc(const char* what, int n, int c, int h, int wd, int s) {
+    MMIF_REQUIRE(n > 0 && c > 0 && h > 0 && wd > 0, "%s: bad extent", what);
+    MMIF_REQUIRE(s >= 2 && s <= PC_MAXS, "%s: kernel = stride must be in [2, %d] (got %d)", what, PC_MAXS, s);
+    MMIF_REQUIRE(h >= s && wd >= s, "%s: the input (%d x %d) is smaller than the kernel (%d)", what, h, wd, s);
+    return MMIF_OK;
+}
+
+extern "C" int mmif_patchconv_fwd(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t s,
+                                  void* stream) {
+    if (int rc = check_pc("patchconv_fwd", n, c, h, wd, s)) return rc;
+    MMIF_REQUIRE(x != nullptr && w != nullptr && y != nullptr, "patchconv_fwd: null pointer");
+    int L = 64;
+    while (L > s * s) L >>= 1;
+    hipLaunchKernelGGL(patchconv_fwd_kernel, dim3(grid1d((long long)n * c * (h / s) * (wd / s) * L)), dim3(256), 0, (hipStream_t)stream, x, w, bias, y,
+                       (long long)n * c, c, h, wd, s, L);
+    return check_launch("patchconv_fwd");
+}
+
+extern "C" int mmif_patchconv_dgrad(const float* gy, const float* w, float* dx, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t s, void* stream) {
+    if (int rc = check_pc("patchconv_dgrad", n, c, h, wd, s)) return rc;
+    MMIF_REQUIRE(gy != nullptr && w != nullptr && dx != nullptr, "patchconv_dgrad: null pointer");
+    hipLaunchKernelGGL(patchconv_dgrad_kernel, dim3(grid1d((long long)n * c * h * wd)), dim3(256), 0, (hipStream_t)stream, gy, w, dx, (long long)n * c, c,
+                       h, wd, s);
+    return check_launch("patchconv_dgrad");
+}
+
+extern "C" size_t mmif_patchconv_wgrad_workspace(int32_t c, int32_t s) {
+    if (c <= 0 || s < 2 || s > PC_MAXS) return 0;
+    return (size_t)PC_CHUNKS * c * (s * s + 1) * sizeof(float);
+}
+
+extern "C" int mmif_patchconv_wgrad(const float* x, const float* gy, float* dw, float* db, int32_t n, int32_t c, int32_t h, int32_t wd, int32_t s,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_pc("patchconv_wgrad", n, c, h, wd, s)) return rc;
+    MMIF_REQUIRE(x != nullptr && gy != nullptr && dw != nullptr && workspace != nullptr, "patchconv_wgrad: null pointer");
+    MMIF_REQUIRE(c <= 65535, "patchconv_wgrad: at most 65535 channels (got %d)", c);
+    if (workspace_bytes < mmif_patchconv_wgrad_workspace(c, s)) {
+        set_error("patchconv_wgrad: workspace of %zu bytes, needs %zu", workspace_bytes, mmif_patchconv_wgrad_workspace(c, s));
+        return MMIF_EWORKSPACE;
+    }
+    const long long rows = (long long)n * (h / s);
+    const long long per = (rows + PC_CHUNKS - 1) / PC_CHUNKS;
+    float* partial = (float*)workspace;
+    hipLaunchKernelGGL(patchconv_wgrad_kernel, dim3(c, PC_CHUNKS), dim3(256), 0, (hipStream_t)stream, x, gy, partial, n, c, h, wd, s, per);
+    if (int rc = check_launch("patchconv_wgrad")) return rc;
+    hipLaunchKernelGGL(patchconv_wgrad_reduce, dim3(cdiv((long long)c * (s * s + 1), 256)), dim3(256), 0, (hipStream_t)stream, partial, dw, db, c, s * s,
+                       PC_CHUNKS);
+    return check_launch("patchconv_wgrad_reduce");
 }

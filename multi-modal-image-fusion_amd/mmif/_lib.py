@@ -85,6 +85,10 @@ SIGNATURES = {
     "mmif_dwconv_fwd": (_i32, [_vp, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     "mmif_dwconv_dgrad": (_i32, [_vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     "mmif_dwconv_wgrad": (_i32, [_vp, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
+    "mmif_patchconv_fwd": (_i32, [_vp, _vp, _vp, _vp] + [_i32] * 5 + [_vp]),
+    "mmif_patchconv_dgrad": (_i32, [_vp, _vp, _vp] + [_i32] * 5 + [_vp]),
+    "mmif_patchconv_wgrad_workspace": (_sz, [_i32, _i32]),
+    "mmif_patchconv_wgrad": (_i32, [_vp, _vp, _vp, _vp] + [_i32] * 5 + [_vp, _sz, _vp]),
     "mmif_channel_sum": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp]),
     "mmif_bilinear_up_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "mmif_bilinear_up_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
@@ -151,6 +155,14 @@ SIGNATURES = {
     "mmif_nonlocal_spatial_workspace": (_sz, [_i32] * 4),
     "mmif_nonlocal_spatial_fwd": (_i32, [_vp] * 4 + [_i32] * 4 + [_vp, _sz, _vp]),
     "mmif_nonlocal_spatial_bwd": (_i32, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
+    "mmif_sra_workspace": (_sz, [_i32, _i32, _i32, _i64, _i64]),
+    "mmif_sra_fwd": (_i32, [_vp] * 5 + [_i32, _i32, _i32, _i64, _i64, _f32, _vp]),
+    "mmif_sra_bwd": (_i32, [_vp] * 9 + [_i32, _i32, _i32, _i64, _i64, _f32, _vp, _sz, _vp]),
+    "mmif_layernorm_fwd": (_i32, [_vp] * 5 + [_i32, _i32, _i64, _f32, _vp]),
+    "mmif_glue_workspace": (_sz, [_i32]),
+    "mmif_layernorm_bwd": (_i32, [_vp] * 7 + [_i32, _i32, _i64, _vp, _sz, _vp]),
+    "mmif_join_fwd": (_i32, [_vp] * 5 + [_i32, _i32, _i64, _i32, _vp]),
+    "mmif_join_bwd": (_i32, [_vp] * 10 + [_i32, _i32, _i64, _i32, _vp, _sz, _vp]),
     "mmif_pairconv_fwd": (_i32, [_TP, _TP, _vp, _vp, _i32, _TP, _TP, _i32, _TP, _TP, _vp]),
     "mmif_pairconv_dgrad": (_i32, [_TP, _TP, _vp, _i32, _TP, _TP, _TP, _TP, _u64, _TP, _vp]),
     "mmif_pairconv_wgrad_workspace": (_sz, []),

@@ -521,6 +521,45 @@ def nonlocal_spatial_bwd(x, y, l, scal, g):
     return dx
 
 
+# ------------------------------------------------------------------ spatial-reduction self-attention core (plain NCHW fp32; csrc/attention.hip)
+SRA_MAX_A = 256
+SRA_HEAD_DIMS = (8, 16, 32)
+
+
+def sra_supported(q, k, v, heads):
+    """CUDA fp32 q [B,A,N], k, v [B,A,M] inside the kernels' limits (include/mmif.h); everything else stays on the tensor-level composition"""
+    if not (q.is_cuda and q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == 3 and k.shape == v.shape and k.shape[:2] == q.shape[:2]):
+        return False
+    b, a, n = q.shape
+    m = k.shape[2]
+    return (heads >= 1 and a % heads == 0 and a // heads in SRA_HEAD_DIMS and a <= SRA_MAX_A and 1 <= b and b * heads <= 65535
+            and 1 <= n < (1 << 30) and 1 <= m < (1 << 30) and b * a * max(n, m) // 256 < 0x7fffffff)
+
+
+def sra_fwd(q, k, v, heads, scale):
+    """o [B,A,N] = softmax_M(scale q^T k) v per head, and the log-sum-exp [B,heads,N] the backward pass needs"""
+    _f32c(q, "q"), _f32c(k, "k"), _f32c(v, "v")
+    b, a, n = q.shape
+    o = torch.empty_like(q)
+    lse = torch.empty((b, heads, n), dtype=torch.float32, device=q.device)
+    check(lib.mmif_sra_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), b, heads, a // heads, n, k.shape[2], float(scale), stream_ptr()), "sra_fwd")
+    return o, lse
+
+
+def sra_bwd(q, k, v, o, lse, go, heads, scale):
+    _f32c(q, "q"), _f32c(k, "k"), _f32c(v, "v"), _f32c(o, "o"), _f32c(lse, "lse"), _f32c(go, "go")
+    b, a, n = q.shape
+    m = k.shape[2]
+    nbytes = lib.mmif_sra_workspace(b, heads, a // heads, n, m)
+    if nbytes == 0:
+        raise _lib.MmifError(f"sra_workspace: {lib.mmif_last_error().decode()}")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    check(lib.mmif_sra_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), _ptr(go), _ptr(dq), _ptr(dk), _ptr(dv), b, heads, a // heads, n, m, float(scale),
+                           _ptr(ws), ws.numel() * 4, stream_ptr()), "sra_bwd")
+    return dq, dk, dv
+
+
 def _d(t):
     return t.d if t is not None else None
 
@@ -751,6 +790,82 @@ def act_bwd(gy, y, act, slope=0.2):
 
 
 # ------------------------------------------------------------------ depth-wise conv (groups == channels)
+def patchconv_fwd(x, w, bias):
+    """depth-wise conv with kernel == stride == w.shape[2], padding 0: x [N,C,H,W] -> [N,C,H//s,W//s]"""
+    _f32c(x, "x"), _f32c(w, "w")
+    n, c, h, wd = x.shape
+    s = w.shape[2]
+    y = torch.empty((n, c, h // s, wd // s), dtype=torch.float32, device=x.device)
+    check(lib.mmif_patchconv_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), n, c, h, wd, s, stream_ptr()), "patchconv_fwd")
+    return y
+
+
+def patchconv_dgrad(gy, w, in_hw):
+    _f32c(gy, "gy"), _f32c(w, "w")
+    n, c = gy.shape[:2]
+    dx = torch.empty((n, c) + tuple(in_hw), dtype=torch.float32, device=gy.device)
+    check(lib.mmif_patchconv_dgrad(_ptr(gy), _ptr(w), _ptr(dx), n, c, in_hw[0], in_hw[1], w.shape[2], stream_ptr()), "patchconv_dgrad")
+    return dx
+
+
+def patchconv_wgrad(x, gy, s, want_bias):
+    _f32c(x, "x"), _f32c(gy, "gy")
+    n, c, h, wd = x.shape
+    dw = torch.empty((c, 1, s, s), dtype=torch.float32, device=x.device)
+    db = torch.empty(c, dtype=torch.float32, device=x.device) if want_bias else None
+    ws = torch.empty(lib.mmif_patchconv_wgrad_workspace(c, s) // 4 + 1, dtype=torch.float32, device=x.device)
+    check(lib.mmif_patchconv_wgrad(_ptr(x), _ptr(gy), _ptr(dw), _ptr(db), n, c, h, wd, s, _ptr(ws), ws.numel() * 4, stream_ptr()), "patchconv_wgrad")
+    return dw, db
+
+
+# ------------------------------------------------------------------ MetaFormer glue (plain NCHW fp32; csrc/glue.hip)
+LAYERNORM_MAX_C = 256
+
+
+def layernorm_fwd(x, weight, bias, eps):
+    """channel LayerNorm of x [N,C,H,W]; returns (y, stats [N,H*W,2] = per-pixel mean and 1 / sqrt(var + eps))"""
+    _f32c(x, "x")
+    n, c, h, w = x.shape
+    y = torch.empty_like(x)
+    stats = torch.empty((n, h * w, 2), dtype=torch.float32, device=x.device)
+    check(lib.mmif_layernorm_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), _ptr(stats), n, c, h * w, float(eps), stream_ptr()), "layernorm_fwd")
+    return y, stats
+
+
+def layernorm_bwd(x, gy, weight, stats, want_weight, want_bias):
+    _f32c(x, "x"), _f32c(gy, "gy")
+    n, c, h, w = x.shape
+    dx = torch.empty_like(x)
+    dw = torch.empty(c, dtype=torch.float32, device=x.device) if want_weight else None
+    db = torch.empty(c, dtype=torch.float32, device=x.device) if want_bias else None
+    ws = torch.empty(lib.mmif_glue_workspace(c) // 4, dtype=torch.float32, device=x.device) if (want_weight or want_bias) else None
+    check(lib.mmif_layernorm_bwd(_ptr(x), _ptr(gy), _ptr(weight), _ptr(stats), _ptr(dx), _ptr(dw), _ptr(db), n, c, h * w, _ptr(ws),
+                                 ws.numel() * 4 if ws is not None else 0, stream_ptr()), "layernorm_bwd")
+    return dx, dw, db
+
+
+def join_fwd(a, b, ls, rs, act):
+    """y = act(ls[c] a + rs[c] b) on [N,C,H,W]; ls / rs may be None; act ACT_NONE | ACT_RELU6"""
+    _f32c(a, "a"), _f32c(b, "b")
+    n, c, h, w = a.shape
+    y = torch.empty_like(a)
+    check(lib.mmif_join_fwd(_ptr(a), _ptr(b), _ptr(ls), _ptr(rs), _ptr(y), n, c, h * w, act, stream_ptr()), "join_fwd")
+    return y
+
+
+def join_bwd(a, b, ls, rs, y, gy, act):
+    """(da, db, dls, drs) of join_fwd; a scale gradient is None where there is no scale"""
+    _f32c(gy, "gy")
+    n, c, h, w = y.shape
+    da, db = torch.empty_like(y), torch.empty_like(y)
+    dls = torch.empty(c, dtype=torch.float32, device=y.device) if ls is not None else None
+    drs = torch.empty(c, dtype=torch.float32, device=y.device) if rs is not None else None
+    ws = torch.empty(lib.mmif_glue_workspace(c) // 4, dtype=torch.float32, device=y.device) if (ls is not None or rs is not None) else None
+    check(lib.mmif_join_bwd(_ptr(a), _ptr(b), _ptr(ls), _ptr(rs), _ptr(y), _ptr(gy), _ptr(da), _ptr(db), _ptr(dls), _ptr(drs), n, c, h * w, act,
+                            _ptr(ws), ws.numel() * 4 if ws is not None else 0, stream_ptr()), "join_bwd")
+    return da, db, dls, drs
+
+
 def dwconv_fwd(x, w, bias, reflect):
     _f32c(x, "x"), _f32c(w, "weight")
     n, c, h, wd = x.shape
