@@ -647,6 +647,36 @@ int mmif_reduce_defer_begin(void* arena, size_t bytes);
 int mmif_reduce_defer_flush(int32_t keep_deferring, void* stream);
 int32_t mmif_reduce_defer_pending(void);
 
+/* Which kernel a ConvLayer call would launch, and on what grid -- a host query that reads the descriptors' geometry only (never `data`,
+ * which may be NULL) and enqueues nothing.  It goes through what the call goes through: the implementation choice (`impl`, dtype), the
+ * entry point's requirements and the route functions of csrc/conv_route.hpp, under the mmif_debug_set_* switches in force.
+ *   op                    a, b       the call
+ *   MMIF_ROUTE_FWD        x, y       mmif_conv2d_reflect_fwd
+ *   MMIF_ROUTE_DGRAD      gy, gx     mmif_conv2d_reflect_dgrad (fold = 0) / _dgrad_folded (fold = 1)
+ *   MMIF_ROUTE_DGRAD_ONTO gy, gx     mmif_conv2d_reflect_dgrad_folded_onto
+ *   MMIF_ROUTE_DGRAD_DUP  gy, gx     mmif_conv2d_reflect_dgrad_folded_dup
+ *   MMIF_ROUTE_WGRAD      x, gy      mmif_conv2d_reflect_wgrad
+ *   MMIF_ROUTE_BWD_PAIR   x, gy      mmif_conv2d_reflect_bwd_pair  (gx: x's extent with a halo of 1)
+ *   MMIF_ROUTE_BWD_WIDE   x, gy      mmif_conv2d_reflect_bwd_wide  (likewise)
+ * num_cus <= 0: the current device's compute units; > 0: that many, and no HIP call is made.  The operand image is taken as given.
+ * Returns 1 and fills *out, or 0 ("not taken": the matching call would refuse these arguments; mmif_last_error may say why).
+ *   name    "mfma<3,2>", "conv1x1_stream", "conv_dma<L1,org1>", "conv_dma<L0,org1,dup>", "thin_async<3>", "thin_wide", "wgrad_dma",
+ *           "wgrad_taprow", "wgrad_mfma<3,4>", "wgrad_mfma<1,4,2,2>", "bwd_pair" ("bwd_pair<reg>" under mmif_debug_set_bwd_pair_dma(0)),
+ *           "x3" / "valu" (fp32 tensors or impl = VALU: the other fields stay 0)
+ *   G       blocks launched; weight gradients: the partial sums per output that the reduce adds (tile groups per channel-group pair)
+ *   slices  of that reduce (0: the call has none)
+ *   tiles   tiles (x M-blocks where a block owns one; conv1x1_stream: 32-pixel runs) the blocks share out
+ *   org     1: the kernel folds the reflect halo itself
+ * MMIF_ROUTE_BWD_WIDE: name, tiles and org of its input-gradient half, G and slices of its weight-gradient half (always wgrad_dma). */
+enum { MMIF_ROUTE_FWD = 0, MMIF_ROUTE_DGRAD = 1, MMIF_ROUTE_DGRAD_ONTO = 2, MMIF_ROUTE_DGRAD_DUP = 3, MMIF_ROUTE_WGRAD = 4, MMIF_ROUTE_BWD_PAIR = 5,
+       MMIF_ROUTE_BWD_WIDE = 6 };
+typedef struct {
+    char name[32];
+    int32_t G, slices, tiles, org;
+} mmif_route;
+int mmif_conv2d_route(int32_t op, const mmif_tensor* a, const mmif_tensor* b, int32_t cin, int32_t cout, int32_t ksize, uint64_t mask_bits,
+                      uint64_t accum_bits, int32_t fold, int32_t impl, int32_t num_cus, mmif_route* out);
+
 /* mmif_dense_encoder_fwd: 2 (default) = the round-5 streaming kernel with 32-column strips, eight waves per CU; 1 = the
  * same with 64-column strips, four waves per CU (csrc/enc_stream2.hip: input-stationary accumulation; every stage within one bf16
  * rounding of its fp64 definition); 0 = the round-2 kernel (csrc/enc_stream.hip, bit-identical to the four layer-wise launches). */

@@ -133,6 +133,7 @@ inline TV make_tv(const mmif_tensor* t) {
 }
 
 int validate_tensor(const mmif_tensor* t, const char* name);
+int validate_extent(const mmif_tensor* t, const char* name);   // the same without `data`: host queries that read geometry only
 // compute units of the current device, cached per device (hipGetDeviceProperties fills a multi-KB struct and can reach the driver: not on the
 // per-launch path -- ADVICE r5); $MMIF_NUM_CUS overrides (experiments: persistent grids on part of the chip)
 int cached_num_cus();

@@ -16,6 +16,7 @@
 //   * epilogue: v_permlane16_swap pairs the two 16-pixel halves so that every lane stores one 16-byte granule per 16-channel fragment.
 // Same k-group order and rounding points as conv_mfma_kernel<1, ...>: results are bit-identical (tests/test_gpu_conv1x1.py).
 #include "common.hpp"
+#include "conv_route.hpp"
 #include <stdlib.h>
 
 namespace mmif {
@@ -23,11 +24,8 @@ namespace mmif {
 typedef __attribute__((ext_vector_type(8))) __bf16 c1_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float c1_f32x4;
 
-constexpr int C1_WAVES = 4;
-constexpr int C1_PX = 32;   // pixels per wave item (two MFMA N tiles)
-
 template <int NMT>
-struct C1Occ { static constexpr int waves_per_eu = NMT <= 4 ? 4 : (NMT <= 8 ? 3 : 2); };
+struct C1Occ { static constexpr int waves_per_eu = c1_waves_per_eu(NMT); };
 
 template <int NMT, bool DGRAD>
 __global__ __launch_bounds__(C1_WAVES * 64, C1Occ<NMT>::waves_per_eu) void conv1x1_stream_kernel(
@@ -169,49 +167,13 @@ __global__ __launch_bounds__(C1_WAVES * 64, C1Occ<NMT>::waves_per_eu) void conv1
     }
 }
 
-static int c1_num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
-static int g_c1_mode = -1;   // mmif_debug_set_conv1x1_stream(0): keep the register-staged kernel (the tests' cross-check)
-constexpr size_t C1_MAX_LDS = 128 * 1024;
-
-static size_t c1_lds_bytes(int nch, int m16p) { return (size_t)nch * 4 * m16p * 16 + (size_t)m16p * 4; }
-
-// shapes the streaming kernel takes; everything else stays on conv_mfma_kernel<1, ...>
-bool conv1x1_stream_ok(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, int n_out, int m16p, uint64_t mask_bits, uint64_t accum_bits) {
-    if (g_c1_mode < 0) g_c1_mode = 1;
-    if (g_c1_mode == 0 || accum_bits != 0) return false;
-    if (tin.hs != tout.hs || tin.ws != tout.ws || tin.n != tout.n) return false;          // same stored geometry: one linear walk
-    if (tin.halo != 0 && !tin.folded) return false;                                       // an unfolded halo-1 gradient needs the fold-on-load path
-    if (m16p > 256 || m16p % 16 != 0 || n_out > m16p) return false;
-    const int nch = (tin.cb + 3) / 4;
-    if (c1_lds_bytes(nch, m16p) > C1_MAX_LDS) return false;
-    if (tin.plane * 16 >= (1ll << 31) || tout.plane * 16 >= (1ll << 31)) return false;      // 32-bit in-plane offsets
-    if (dgrad && mask_bits != 0) {
-        if (tmask.halo != 0 || tmask.h != tout.h || tmask.w != tout.w || tmask.n != tout.n || tmask.plane * 16 >= (1ll << 31)) return false;
-    }
-    return (long long)tin.n * cdiv(tin.plane, C1_PX) < (1ll << 31);
-}
-
+// the shapes this kernel takes (everything else stays on conv_mfma_kernel<1, ...>) and its grid: conv_route(), csrc/conv_route.hpp
 template <int NMT>
-static int c1_launch(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out, int m16p, int relu,
-                     uint64_t mask_bits, hipStream_t st) {
-    const int nch = (tin.cb + 3) / 4;
+static int c1_launch(const ConvRoute& r, bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out,
+                     int relu, uint64_t mask_bits, hipStream_t st) {
+    const int nch = (tin.cb + 3) / 4, m16p = n_mblocks(n_out) * r.mf * 16;
     const size_t lds = c1_lds_bytes(nch, m16p);
-    const int groups = cdiv(tin.plane, C1_PX), total = groups * tin.n;
-    int bpc = (int)((160 * 1024) / (lds + 512));
-    bpc = bpc < 1 ? 1 : (bpc > C1Occ<NMT>::waves_per_eu ? C1Occ<NMT>::waves_per_eu : bpc);
-    int grid = c1_num_cus() * bpc;
-    if (grid > cdiv(total, C1_WAVES)) grid = cdiv(total, C1_WAVES);
-    if (grid < 1) grid = 1;
+    const int groups = cdiv(tin.plane, C1_PX), total = (int)r.items, grid = r.G;
     if (dgrad) {
         static size_t set_d = 0;
         if (lds > set_d) {
@@ -240,15 +202,13 @@ static int c1_launch(bool dgrad, const TV& tin, const TV& tout, const TV& tmask,
     return check_launch(dgrad ? "conv1x1_stream dgrad" : "conv1x1_stream fwd");
 }
 
-int conv1x1_stream(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out, int m16p, int relu,
-                   uint64_t mask_bits, hipStream_t st) {
+int conv1x1_stream(const ConvRoute& r, bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out,
+                   int relu, uint64_t mask_bits, hipStream_t st) {
     const int nmt = (n_out + 15) / 16;
-    if (nmt <= 4) return c1_launch<4>(dgrad, tin, tout, tmask, wpk, bias, n_out, m16p, relu, mask_bits, st);
-    if (nmt <= 8) return c1_launch<8>(dgrad, tin, tout, tmask, wpk, bias, n_out, m16p, relu, mask_bits, st);
-    if (nmt <= 12) return c1_launch<12>(dgrad, tin, tout, tmask, wpk, bias, n_out, m16p, relu, mask_bits, st);
-    return c1_launch<16>(dgrad, tin, tout, tmask, wpk, bias, n_out, m16p, relu, mask_bits, st);
+    if (nmt <= 4) return c1_launch<4>(r, dgrad, tin, tout, tmask, wpk, bias, n_out, relu, mask_bits, st);
+    if (nmt <= 8) return c1_launch<8>(r, dgrad, tin, tout, tmask, wpk, bias, n_out, relu, mask_bits, st);
+    if (nmt <= 12) return c1_launch<12>(r, dgrad, tin, tout, tmask, wpk, bias, n_out, relu, mask_bits, st);
+    return c1_launch<16>(r, dgrad, tin, tout, tmask, wpk, bias, n_out, relu, mask_bits, st);
 }
 
 }  // namespace mmif
-
-extern "C" void mmif_debug_set_conv1x1_stream(int32_t mode) { mmif::g_c1_mode = mode ? 1 : 0; }

@@ -1,6 +1,7 @@
 // C-ABI entry points of the generic ConvLayer kernels: argument validation + dispatch between the
 // VALU (fp32 parity) and MFMA (bf16 throughput) implementations.
 #include "common.hpp"
+#include "conv_route.hpp"
 
 namespace mmif {
 // conv_valu.hip
@@ -21,7 +22,6 @@ bool wgrad_mfma_supported(int ks, int cin, int cout);
 size_t wgrad_mfma_workspace(int cin, int cout, int ks);
 int wgrad_mfma(int ks, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
                hipStream_t st);
-bool bwd_pair_supported(int ks, int cin, int cout);
 size_t bwd_pair_workspace(int cin, int cout);
 int bwd_pair(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
              hipStream_t st);
@@ -66,17 +66,67 @@ static int pick_impl(int impl, int dtype, bool mfma_ok, const char* what, bool x
     return impl;
 }
 
-extern "C" int mmif_conv2d_reflect_fwd(const mmif_tensor* x, const float* w, const void* w_packed, const float* bias,
-                                       const mmif_tensor* y, int32_t cin, int32_t cout, int32_t ksize, int32_t relu,
-                                       int32_t impl, void* stream) {
-    if (int rc = validate_tensor(x, "x")) return rc;
-    if (int rc = validate_tensor(y, "y")) return rc;
+// the accumulate-onto and the masked-copies forms of the folded dgrad: bf16, gy a folded halo-1 gradient, gx with a halo of 1
+static bool folded_bf16_pair(const mmif_tensor* gy, const mmif_tensor* gx) {
+    return gy->dtype == MMIF_BF16 && gx->dtype == MMIF_BF16 && gy->halo == 1 && (gy->flags & MMIF_T_FOLDED) && gx->halo == 1;
+}
+// What each entry point requires of its descriptors (never of `data`): the call and mmif_conv2d_route ask the same function.
+static int fwd_check(const mmif_tensor* x, const mmif_tensor* y, int32_t cin, int32_t cout, int32_t ksize) {
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "conv2d_reflect_fwd: ksize must be 1 or 3 (got %d)", ksize);
     MMIF_REQUIRE(x->halo == 0 && y->halo == 0, "conv2d_reflect_fwd: activations must have halo 0");
     MMIF_REQUIRE(x->dtype == y->dtype && x->n == y->n && x->h == y->h && x->w == y->w, "conv2d_reflect_fwd: x/y mismatch");
     MMIF_REQUIRE(cin > 0 && (cin + 7) / 8 == x->cb, "conv2d_reflect_fwd: cin=%d does not match x.cb=%d", cin, x->cb);
     MMIF_REQUIRE(cout > 0 && (cout + 7) / 8 == y->cb, "conv2d_reflect_fwd: cout=%d does not match y.cb=%d", cout, y->cb);
     MMIF_REQUIRE(ksize == 1 || (x->h >= 2 && x->w >= 2), "reflect padding needs h,w >= 2");
+    return MMIF_OK;
+}
+static int dgrad_check(const char* what, const mmif_tensor* gy, const mmif_tensor* gx, int32_t cin, int32_t cout, int32_t ksize) {
+    MMIF_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize must be 1 or 3 (got %d)", what, ksize);
+    MMIF_REQUIRE(gx->halo >= ksize / 2, "%s: gx needs halo >= ksize/2", what);
+    MMIF_REQUIRE(gy->dtype == gx->dtype && gy->n == gx->n && gy->h == gx->h && gy->w == gx->w, "%s: gy/gx mismatch", what);
+    MMIF_REQUIRE(cin > 0 && (cin + 7) / 8 == gx->cb, "%s: cin=%d does not match gx.cb=%d", what, cin, gx->cb);
+    MMIF_REQUIRE(cout > 0 && (cout + 7) / 8 == gy->cb, "%s: cout=%d does not match gy.cb=%d", what, cout, gy->cb);
+    return MMIF_OK;
+}
+static int wgrad_check(const mmif_tensor* x, const mmif_tensor* gy, int32_t cin, int32_t cout, int32_t ksize) {
+    MMIF_REQUIRE(ksize == 1 || ksize == 3, "conv2d_reflect_wgrad: ksize must be 1 or 3 (got %d)", ksize);
+    MMIF_REQUIRE(x->halo == 0, "conv2d_reflect_wgrad: x must be an activation (halo 0)");
+    MMIF_REQUIRE(x->dtype == gy->dtype && x->n == gy->n && x->h == gy->h && x->w == gy->w, "conv2d_reflect_wgrad: x/gy mismatch");
+    MMIF_REQUIRE(cin > 0 && (cin + 7) / 8 == x->cb, "conv2d_reflect_wgrad: cin=%d does not match x.cb=%d", cin, x->cb);
+    MMIF_REQUIRE(cout > 0 && (cout + 7) / 8 == gy->cb, "conv2d_reflect_wgrad: cout=%d does not match gy.cb=%d", cout, gy->cb);
+    return MMIF_OK;
+}
+// (the one-call backwards: what they require of x and gy; gx is x's shape with a halo of 1)
+static int pair_check(const mmif_tensor* gy, const mmif_tensor* x, int32_t cin, int32_t cout, int32_t ksize) {
+    MMIF_REQUIRE(bwd_pair_supported(ksize, cin, cout), "conv2d_reflect_bwd_pair: unsupported layer %d -> %d k%d", cin, cout, ksize);
+    MMIF_REQUIRE(gy->dtype == MMIF_BF16 && x->dtype == MMIF_BF16, "conv2d_reflect_bwd_pair: bf16 tensors expected");
+    MMIF_REQUIRE(gy->halo == 1 && (gy->flags & MMIF_T_FOLDED), "conv2d_reflect_bwd_pair: gy must be a folded halo-1 gradient");
+    MMIF_REQUIRE(x->halo == 0, "conv2d_reflect_bwd_pair: x halo 0, gx halo 1 expected");
+    MMIF_REQUIRE(gy->n == x->n && gy->h == x->h && gy->w == x->w, "conv2d_reflect_bwd_pair: shape mismatch");
+    MMIF_REQUIRE((cin + 7) / 8 == x->cb && (cout + 7) / 8 == gy->cb, "conv2d_reflect_bwd_pair: channel blocks do not match");
+    MMIF_REQUIRE(x->h >= 4 && x->w >= 4, "conv2d_reflect_bwd_pair: needs h, w >= 4 (fold steps inside the border tiles)");
+    MMIF_REQUIRE((long long)x->cb_total * x->h * x->w < (1ll << 31) && (long long)gy->cb_total * (gy->h + 2) * (gy->w + 2) < (1ll << 31),
+                 "conv2d_reflect_bwd_pair: one image of x / gy must stay below 2^31 granules (32-bit tile offsets)");
+    return MMIF_OK;
+}
+static int wide_check(const mmif_tensor* gy, const mmif_tensor* x, int32_t cin, int32_t cout, int32_t ksize) {
+    MMIF_REQUIRE(bwd_wide_supported(ksize, cin, cout), "conv2d_reflect_bwd_wide: unsupported layer %d -> %d k%d", cin, cout, ksize);
+    MMIF_REQUIRE(gy->dtype == MMIF_BF16 && x->dtype == MMIF_BF16, "conv2d_reflect_bwd_wide: bf16 tensors expected");
+    MMIF_REQUIRE(gy->halo == 1 && (gy->flags & MMIF_T_FOLDED), "conv2d_reflect_bwd_wide: gy must be a folded halo-1 gradient");
+    MMIF_REQUIRE(x->halo == 0, "conv2d_reflect_bwd_wide: x halo 0, gx halo 1 expected");
+    MMIF_REQUIRE(gy->n == x->n && gy->h == x->h && gy->w == x->w, "conv2d_reflect_bwd_wide: shape mismatch");
+    MMIF_REQUIRE(cin / 8 == x->cb && cout / 8 == gy->cb, "conv2d_reflect_bwd_wide: channel blocks do not match");
+    MMIF_REQUIRE(x->h >= 4 && x->w >= 4, "conv2d_reflect_bwd_wide: needs h, w >= 4 (fold steps inside the border tiles)");
+    MMIF_REQUIRE((long long)(x->h + 2) * (x->w + 2) * 16 * 8 < (1ll << 31), "conv2d_reflect_bwd_wide: 8 channel planes must stay below 2 GiB (32-bit staging offsets)");
+    return MMIF_OK;
+}
+
+extern "C" int mmif_conv2d_reflect_fwd(const mmif_tensor* x, const float* w, const void* w_packed, const float* bias,
+                                       const mmif_tensor* y, int32_t cin, int32_t cout, int32_t ksize, int32_t relu,
+                                       int32_t impl, void* stream) {
+    if (int rc = validate_tensor(x, "x")) return rc;
+    if (int rc = validate_tensor(y, "y")) return rc;
+    if (int rc = fwd_check(x, y, cin, cout, ksize)) return rc;
     TV tx = make_tv(x), ty = make_tv(y);
     const int im = pick_impl(impl, x->dtype, conv_mfma_supported(false, ksize, cin, cout) && w_packed != nullptr, "conv2d_reflect_fwd",
                              x->dtype == MMIF_F32 && w_packed != nullptr && conv_x3_supported(false, ksize, cin, cout, tx, ty));
@@ -92,11 +142,7 @@ static int dgrad_impl(const char* what, const mmif_tensor* gy, const float* w, c
                       int32_t impl, void* stream, bool fold, const mmif_tensor* gx_old = nullptr) {
     if (int rc = validate_tensor(gy, "gy")) return rc;
     if (int rc = validate_tensor(gx, "gx")) return rc;
-    MMIF_REQUIRE(ksize == 1 || ksize == 3, "%s: ksize must be 1 or 3 (got %d)", what, ksize);
-    MMIF_REQUIRE(gx->halo >= ksize / 2, "%s: gx needs halo >= ksize/2", what);
-    MMIF_REQUIRE(gy->dtype == gx->dtype && gy->n == gx->n && gy->h == gx->h && gy->w == gx->w, "%s: gy/gx mismatch", what);
-    MMIF_REQUIRE(cin > 0 && (cin + 7) / 8 == gx->cb, "%s: cin=%d does not match gx.cb=%d", what, cin, gx->cb);
-    MMIF_REQUIRE(cout > 0 && (cout + 7) / 8 == gy->cb, "%s: cout=%d does not match gy.cb=%d", what, cout, gy->cb);
+    if (int rc = dgrad_check(what, gy, gx, cin, cout, ksize)) return rc;
     TV tg = make_tv(gy), tgx = make_tv(gx), tm = tgx;
     if (mask_bits) {
         MMIF_REQUIRE(x != nullptr, "%s: mask_bits set but x is NULL", what);
@@ -148,7 +194,7 @@ extern "C" int mmif_conv2d_reflect_dgrad_folded(const mmif_tensor* gy, const flo
 // comes from ANOTHER tensor (DenseFuse / VIFNet: both encoder branches start from the one gradient of f1 + f2 -- no per-branch copy).
 extern "C" int mmif_conv2d_dgrad_onto_supported(const mmif_tensor* gy, const mmif_tensor* gx, int32_t cin, int32_t cout, int32_t ksize) {
     if (validate_tensor(gy, "gy") != MMIF_OK || validate_tensor(gx, "gx") != MMIF_OK) return 0;
-    if (gy->dtype != MMIF_BF16 || gx->dtype != MMIF_BF16 || gy->halo != 1 || !(gy->flags & MMIF_T_FOLDED) || gx->halo != 1) return 0;
+    if (!folded_bf16_pair(gy, gx)) return 0;
     return conv_dgrad_onto_supported(ksize, cin, cout, make_tv(gy), make_tv(gx)) ? 1 : 0;
 }
 extern "C" int mmif_conv2d_reflect_dgrad_folded_onto(const mmif_tensor* gy, const void* w_packed_t, const mmif_tensor* x, const mmif_tensor* gx_old,
@@ -164,7 +210,7 @@ extern "C" int mmif_conv2d_reflect_dgrad_folded_onto(const mmif_tensor* gy, cons
 extern "C" int mmif_conv2d_dgrad_dup_supported(const mmif_tensor* gy, const mmif_tensor* gx, int32_t cin, int32_t cout, int32_t ksize) {
     (void)cout;
     if (validate_tensor(gy, "gy") != MMIF_OK || validate_tensor(gx, "gx") != MMIF_OK) return 0;
-    if (gy->dtype != MMIF_BF16 || gx->dtype != MMIF_BF16 || gy->halo != 1 || !(gy->flags & MMIF_T_FOLDED) || gx->halo != 1) return 0;
+    if (!folded_bf16_pair(gy, gx)) return 0;
     return conv_dgrad_dup_supported(ksize, cin, make_tv(gy), make_tv(gx)) ? 1 : 0;
 }
 extern "C" int mmif_conv2d_reflect_dgrad_folded_dup(const mmif_tensor* gy, const void* w_packed_t, const mmif_tensor* gx, int32_t cin, int32_t cout,
@@ -199,11 +245,7 @@ extern "C" int mmif_conv2d_reflect_wgrad(const mmif_tensor* x, const mmif_tensor
                                          size_t workspace_bytes, int32_t impl, void* stream) {
     if (int rc = validate_tensor(x, "x")) return rc;
     if (int rc = validate_tensor(gy, "gy")) return rc;
-    MMIF_REQUIRE(ksize == 1 || ksize == 3, "conv2d_reflect_wgrad: ksize must be 1 or 3 (got %d)", ksize);
-    MMIF_REQUIRE(x->halo == 0, "conv2d_reflect_wgrad: x must be an activation (halo 0)");
-    MMIF_REQUIRE(x->dtype == gy->dtype && x->n == gy->n && x->h == gy->h && x->w == gy->w, "conv2d_reflect_wgrad: x/gy mismatch");
-    MMIF_REQUIRE(cin > 0 && (cin + 7) / 8 == x->cb, "conv2d_reflect_wgrad: cin=%d does not match x.cb=%d", cin, x->cb);
-    MMIF_REQUIRE(cout > 0 && (cout + 7) / 8 == gy->cb, "conv2d_reflect_wgrad: cout=%d does not match gy.cb=%d", cout, gy->cb);
+    if (int rc = wgrad_check(x, gy, cin, cout, ksize)) return rc;
     MMIF_REQUIRE(dw != nullptr, "conv2d_reflect_wgrad: dw is NULL");
     if (workspace_bytes < mmif_conv2d_wgrad_workspace(cin, cout, ksize)) {
         set_error("conv2d_reflect_wgrad: workspace too small (%zu < %zu)", workspace_bytes, mmif_conv2d_wgrad_workspace(cin, cout, ksize));
@@ -228,16 +270,12 @@ extern "C" int mmif_conv2d_reflect_bwd_pair(const mmif_tensor* gy, const void* w
     if (int rc = validate_tensor(gy, "gy")) return rc;
     if (int rc = validate_tensor(x, "x")) return rc;
     if (int rc = validate_tensor(gx, "gx")) return rc;
-    MMIF_REQUIRE(bwd_pair_supported(ksize, cin, cout), "conv2d_reflect_bwd_pair: unsupported layer %d -> %d k%d", cin, cout, ksize);
+    if (int rc = pair_check(gy, x, cin, cout, ksize)) return rc;
     MMIF_REQUIRE(w_packed_t != nullptr && dw != nullptr, "conv2d_reflect_bwd_pair: NULL operand image / dw");
-    MMIF_REQUIRE(gy->dtype == MMIF_BF16 && x->dtype == MMIF_BF16 && gx->dtype == MMIF_BF16, "conv2d_reflect_bwd_pair: bf16 tensors expected");
-    MMIF_REQUIRE(gy->halo == 1 && (gy->flags & MMIF_T_FOLDED), "conv2d_reflect_bwd_pair: gy must be a folded halo-1 gradient");
-    MMIF_REQUIRE(x->halo == 0 && gx->halo == 1, "conv2d_reflect_bwd_pair: x halo 0, gx halo 1 expected");
-    MMIF_REQUIRE(gy->n == x->n && gy->h == x->h && gy->w == x->w && gx->n == x->n && gx->h == x->h && gx->w == x->w, "conv2d_reflect_bwd_pair: shape mismatch");
-    MMIF_REQUIRE((cin + 7) / 8 == x->cb && x->cb == gx->cb && (cout + 7) / 8 == gy->cb, "conv2d_reflect_bwd_pair: channel blocks do not match");
-    MMIF_REQUIRE(x->h >= 4 && x->w >= 4, "conv2d_reflect_bwd_pair: needs h, w >= 4 (fold steps inside the border tiles)");
-    MMIF_REQUIRE((long long)x->cb_total * x->h * x->w < (1ll << 31) && (long long)gy->cb_total * (gy->h + 2) * (gy->w + 2) < (1ll << 31),
-                 "conv2d_reflect_bwd_pair: one image of x / gy must stay below 2^31 granules (32-bit tile offsets)");
+    MMIF_REQUIRE(gx->dtype == MMIF_BF16, "conv2d_reflect_bwd_pair: bf16 tensors expected");
+    MMIF_REQUIRE(gx->halo == 1, "conv2d_reflect_bwd_pair: x halo 0, gx halo 1 expected");
+    MMIF_REQUIRE(gx->n == x->n && gx->h == x->h && gx->w == x->w, "conv2d_reflect_bwd_pair: shape mismatch");
+    MMIF_REQUIRE(x->cb == gx->cb, "conv2d_reflect_bwd_pair: channel blocks do not match");
     if (workspace == nullptr || workspace_bytes < bwd_pair_workspace(cin, cout)) {
         set_error("conv2d_reflect_bwd_pair: workspace too small");
         return MMIF_EWORKSPACE;
@@ -294,15 +332,12 @@ extern "C" int mmif_conv2d_reflect_bwd_wide(const mmif_tensor* gy, const void* w
         if (int rc = conv_x3(true, tg, tgx, tx, w_packed_t, nullptr, cin, cout, 0, mask_bits, 0, (hipStream_t)stream, ksize, (const unsigned*)signs, &folded)) return rc;
         return (ksize == 1 || folded) ? MMIF_OK : mmif_fold_halo(gx, stream);
     }
-    MMIF_REQUIRE(bwd_wide_supported(ksize, cin, cout), "conv2d_reflect_bwd_wide: unsupported layer %d -> %d k%d", cin, cout, ksize);
+    if (int rc = wide_check(gy, x, cin, cout, ksize)) return rc;
     MMIF_REQUIRE(w_packed_t != nullptr && dw != nullptr, "conv2d_reflect_bwd_wide: NULL operand image / dw");
-    MMIF_REQUIRE(gy->dtype == MMIF_BF16 && x->dtype == MMIF_BF16 && gx->dtype == MMIF_BF16, "conv2d_reflect_bwd_wide: bf16 tensors expected");
-    MMIF_REQUIRE(gy->halo == 1 && (gy->flags & MMIF_T_FOLDED), "conv2d_reflect_bwd_wide: gy must be a folded halo-1 gradient");
-    MMIF_REQUIRE(x->halo == 0 && gx->halo == 1, "conv2d_reflect_bwd_wide: x halo 0, gx halo 1 expected");
-    MMIF_REQUIRE(gy->n == x->n && gy->h == x->h && gy->w == x->w && gx->n == x->n && gx->h == x->h && gx->w == x->w, "conv2d_reflect_bwd_wide: shape mismatch");
-    MMIF_REQUIRE(cin / 8 == x->cb && x->cb == gx->cb && cout / 8 == gy->cb, "conv2d_reflect_bwd_wide: channel blocks do not match");
-    MMIF_REQUIRE(x->h >= 4 && x->w >= 4, "conv2d_reflect_bwd_wide: needs h, w >= 4 (fold steps inside the border tiles)");
-    MMIF_REQUIRE((long long)(x->h + 2) * (x->w + 2) * 16 * 8 < (1ll << 31), "conv2d_reflect_bwd_wide: 8 channel planes must stay below 2 GiB (32-bit staging offsets)");
+    MMIF_REQUIRE(gx->dtype == MMIF_BF16, "conv2d_reflect_bwd_wide: bf16 tensors expected");
+    MMIF_REQUIRE(gx->halo == 1, "conv2d_reflect_bwd_wide: x halo 0, gx halo 1 expected");
+    MMIF_REQUIRE(gx->n == x->n && gx->h == x->h && gx->w == x->w, "conv2d_reflect_bwd_wide: shape mismatch");
+    MMIF_REQUIRE(x->cb == gx->cb, "conv2d_reflect_bwd_wide: channel blocks do not match");
     if (workspace == nullptr || workspace_bytes < wgrad_mfma_workspace(cin, cout, ksize)) {
         set_error("conv2d_reflect_bwd_wide: workspace too small");
         return MMIF_EWORKSPACE;
@@ -313,4 +348,87 @@ extern "C" int mmif_conv2d_reflect_bwd_wide(const mmif_tensor* gy, const void* w
     }
     return bwd_wide(make_tv(x), make_tv(gy), make_tv(gx), w_packed_t, dw, db, cin, cout, mask_bits, accumulate, (float*)workspace,
                     (unsigned char*)signs, (hipStream_t)stream, phase);
+}
+
+// ---- which kernel a call would launch, and on what grid (include/mmif.h): pick_impl(), the entry point's own requirements and the
+// route functions of csrc/conv_route.hpp -- the ones the calls above go through.  Reads geometry only, never `data`.
+static TV halo1_like(const TV& t) {   // gx of the one-call backwards: x's extent with a halo of 1
+    TV v = t;
+    v.halo = 1; v.hs = t.h + 2; v.ws = t.w + 2; v.folded = 0;
+    v.plane = (long long)v.hs * v.ws;
+    v.img = (long long)v.cb_total * v.plane;
+    return v;
+}
+extern "C" int mmif_conv2d_route(int32_t op, const mmif_tensor* a, const mmif_tensor* b, int32_t cin, int32_t cout, int32_t ksize, uint64_t mask_bits,
+                                 uint64_t accum_bits, int32_t fold, int32_t impl, int32_t num_cus, mmif_route* out) {
+    if (out == nullptr) return 0;
+    memset(out, 0, sizeof(*out));
+    if (validate_extent(a, "a") != MMIF_OK || validate_extent(b, "b") != MMIF_OK) return 0;
+    const TV ta = make_tv(a), tb = make_tv(b);
+    const bool f32 = a->dtype == MMIF_F32;
+    const bool dgrad = op == MMIF_ROUTE_DGRAD || op == MMIF_ROUTE_DGRAD_ONTO || op == MMIF_ROUTE_DGRAD_DUP;
+    int im;
+    if (op == MMIF_ROUTE_FWD) {
+        if (fwd_check(a, b, cin, cout, ksize) != MMIF_OK) return 0;
+        im = pick_impl(impl, a->dtype, conv_mfma_supported(false, ksize, cin, cout), "conv2d_route", f32 && conv_x3_supported(false, ksize, cin, cout, ta, tb));
+    } else if (dgrad) {
+        if (dgrad_check("conv2d_route", a, b, cin, cout, ksize) != MMIF_OK) return 0;
+        if (op != MMIF_ROUTE_DGRAD && !folded_bf16_pair(a, b)) return 0;
+        im = op != MMIF_ROUTE_DGRAD ? MMIF_IMPL_MFMA
+                                    : pick_impl(impl, a->dtype, conv_mfma_supported(true, ksize, cin, cout), "conv2d_route",
+                                                f32 && conv_x3_supported(true, ksize, cin, cout, ta, tb));
+    } else if (op == MMIF_ROUTE_WGRAD) {
+        if (wgrad_check(a, b, cin, cout, ksize) != MMIF_OK) return 0;
+        im = pick_impl(impl, a->dtype, wgrad_mfma_supported(ksize, cin, cout), "conv2d_route", f32 && wgrad_x3_supported(ksize, cin, cout, ta, tb));
+    } else if (op == MMIF_ROUTE_BWD_PAIR) {
+        if (pair_check(b, a, cin, cout, ksize) != MMIF_OK) return 0;
+        im = MMIF_IMPL_MFMA;
+    } else if (op == MMIF_ROUTE_BWD_WIDE) {
+        if (f32 && b->dtype == MMIF_F32) {   // fp32 tensors: the split-operand pair of kernels, where they take the layer
+            if (!(a->halo == 0 && a->n == b->n && a->h == b->h && a->w == b->w && (cin + 7) / 8 == a->cb && (cout + 7) / 8 == b->cb &&
+                  wgrad_x3_supported(ksize, cin, cout, ta, tb) && conv_x3_supported(true, ksize, cin, cout, tb, halo1_like(ta))))
+                return 0;
+            im = MMIF_IMPL_X3;
+        } else {
+            if (wide_check(b, a, cin, cout, ksize) != MMIF_OK) return 0;
+            im = MMIF_IMPL_MFMA;
+        }
+    } else {
+        set_error("conv2d_route: bad op %d", op);
+        return 0;
+    }
+    if (im < 0) return 0;
+    if (im != MMIF_IMPL_MFMA) {
+        snprintf(out->name, sizeof(out->name), "%s", im == MMIF_IMPL_X3 ? "x3" : "valu");
+        return 1;
+    }
+    if (num_cus <= 0) num_cus = cached_num_cus();
+    const ConvSwitches& sw = g_conv_switches;
+    if (op == MMIF_ROUTE_WGRAD || op == MMIF_ROUTE_BWD_WIDE) {   // (bwd_wide: G and slices of its weight-gradient half ...)
+        const WgradRoute r = wgrad_route(ksize, cin, cout, ta, tb, num_cus, sw, op == MMIF_ROUTE_BWD_WIDE);
+        if (r.kernel == WgradRoute::NONE) return 0;
+        route_name(r, out->name, sizeof(out->name));
+        out->G = r.G; out->slices = r.slices; out->tiles = r.total;
+        if (op == MMIF_ROUTE_WGRAD) return 1;
+    }
+    if (op == MMIF_ROUTE_BWD_PAIR) {
+        const PairRoute r = pair_route(ksize, cin, cout, ta, tb, num_cus, sw);
+        if (r.kernel == PairRoute::NONE) return 0;
+        route_name(r, out->name, sizeof(out->name));
+        out->G = r.G; out->slices = r.slices; out->tiles = r.total; out->org = 1;
+        return 1;
+    }
+    // forward / input gradient (... bwd_wide: name, tiles and org of its input-gradient half)
+    const bool wide = op == MMIF_ROUTE_BWD_WIDE;
+    const ConvForm form = wide ? ConvForm::WIDE_SIGNS : op == MMIF_ROUTE_DGRAD_ONTO ? ConvForm::ONTO : op == MMIF_ROUTE_DGRAD_DUP ? ConvForm::DUP : ConvForm::PLAIN;
+    const ConvRoute r = wide ? conv_route(true, ksize, tb, halo1_like(ta), cin, mask_bits, 0, true, form, num_cus, sw)
+                             : conv_route(dgrad, ksize, ta, tb, dgrad ? cin : cout, mask_bits, accum_bits, fold != 0 || form != ConvForm::PLAIN, form, num_cus, sw);
+    if (r.kernel == ConvRoute::NONE || (form == ConvForm::ONTO && r.kernel != ConvRoute::THIN_ASYNC)) {
+        memset(out, 0, sizeof(*out));
+        return 0;
+    }
+    route_name(r, out->name, sizeof(out->name));
+    out->tiles = (int32_t)r.items; out->org = r.org;
+    if (!wide) out->G = r.G;
+    return 1;
 }

@@ -20,6 +20,7 @@
 // layout, so fragments are fetched with the gfx950 LDS transpose read ds_read_b64_tr_b16
 // (4 pixels x 16 channels per 16-lane group -> per lane 4 consecutive pixels of one channel).
 #include "common.hpp"
+#include "conv_route.hpp"
 #include "wgrad_reduce.hpp"
 // the epilogues' 16-byte output stores.  (Round 5 tried them as inline-asm `global_store_dwordx4 ... sc0`, after the sc0 bit had made the
 // streaming encoder's buffer stores 5 % faster: no change in the step once the asm was correct -- a first version without the two wait
@@ -36,25 +37,14 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 
-constexpr int MT = 16;        // output tile edge
-constexpr int DT_ROWS_C = 32; // rows of a conv_dma_kernel tile (= DT_ROWS below)
-constexpr int CHUNK_CB = 4;   // channel blocks per K chunk
-
+constexpr int DT_ROWS_C = DT_ROWS;   // rows of a conv_dma_kernel tile, as the shared epilogues spell it
 __host__ __device__ constexpr int plane_granules(int ks) { return ks == 3 ? 336 : 256; }  // bytes = 0 mod 256
 
-static inline int pick_mf(int n_out) {
-    const int fr = (n_out + 15) / 16;
-    return fr <= 4 ? fr : 4;
-}
 // Order in which every 3x3 kernel of this file visits the taps: COLUMN-major -- (u, v) = (0,0), (1,0), (2,0), (0,1), ... -- so that
 // the three steps of one column offset v read the same six tile rows (conv_dma_kernel keeps them in registers: 6 instead of 12
 // operand fragments per column).  All kernels share the order, hence the summation order, hence stay bit-identical to each other.
 __host__ __device__ inline int visit_tap(int i, int ks) { return ks == 3 ? (i % 3) * 3 + i / 3 : i; }
 
-static inline int n_mblocks(int n_out) {
-    const int fr = (n_out + 15) / 16, mf = pick_mf(n_out);
-    return (fr + mf - 1) / mf;
-}
 // packed image: for each chunk, nkg_pad(chunk) k-group planes of [M16p][8] bf16, M16p = n_mblocks*MF*16
 static size_t packed_bytes(int n_out, int n_in, int ks) {
     const int ncb = (n_in + 7) / 8, kk = ks * ks;
@@ -644,8 +634,6 @@ __global__ __launch_bounds__(256, MF == 1 ? 4 : 2) void conv_mfma_kernel(TV tin,
 // (tile, M-block) items (XCD-contiguous bands, as above), so the first chunk of the next tile is in flight during the last
 // chunk of the current one, and a tile's epilogue (stores) runs after the NEXT chunk's DMAs are issued.
 // Requires the input gradient of a dgrad to be a FOLDED halo-1 tensor (mmif_fold_halo): its zeroed halo ring is the zero fill.
-constexpr int DT_ROWS = 32;                          // output tile rows (8 waves x 4)
-static_assert(DT_ROWS == DT_ROWS_C, "tile rows");
 constexpr int DTP_Y = DT_ROWS + 2, DTP_X = MT + 2;   // 34 x 18 input tile
 constexpr int DPL = 624;                             // granules per LDS plane (612 used); 9984 B = 0 mod 256
 constexpr int DIN_PIECES = CHUNK_CB * DPL / 64;      // 39 DMA pieces (64 granules = 1 KiB each)
@@ -1191,11 +1179,6 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
 //   * NO block barrier in the steady state: loaders publish "tile landed" and consumers "slot free" through LDS counters
 //     (ds_add_u32 by lane 0, polled with s_sleep), so the two groups and the loaders drift freely against each other.
 // Spin loops are bounded (a failed hand-off would produce wrong numbers, never a hung GPU).
-constexpr int TN_MAXCB = 6;                    // input channel blocks per tile (cin <= 48)
-constexpr int TN_PL = 336;                     // granules per LDS plane (18x18 = 324 used); 5376 B = 0 mod 256
-constexpr int TN_MAXKG = 2 * 36;               // k-group planes of two chunks
-constexpr int TN_GROUPS = 3, TN_LOAD = 4, TN_MAXSLOTS = 8;   // 12 consumer + 4 loader waves = one 1024-thread block per CU
-__host__ __device__ constexpr int tn_ring_bytes(int mf) { return mf == 1 ? 128 * 1024 : (mf == 2 ? 112 * 1024 : 96 * 1024); }
 
 __device__ inline void tn_wait_vmcnt(int n) {   // s_waitcnt vmcnt(n), n wave-uniform in 0..16 (the immediate must be a constant)
     switch (n) {
@@ -1806,8 +1789,6 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
         }
 }
 
-// ------------------------------------------------------------------ host side
-static long long* g_trace = nullptr;  // device buffer [1024][64] for the optional phase trace
 // ------------------------------------------------------------------ fused backward of ONE thin 3x3 layer: dgrad + wgrad ("bwd pair")
 // decode.2 (64 -> 32) and decode.3 (32 -> 16) of every PFNet / DenseFuse decoder: their dgrad (read g + the ReLU-mask activations x, write
 // gx) and their wgrad (read x + g again) move 256 / 128 planes for 160 / 80 of data.  Here a block stages ONE 18 x 18 tile of g (zero
@@ -2290,54 +2271,42 @@ __global__ __launch_bounds__(512, NXB == 4 ? 1 : 2) void bwd_pair_dma_kernel(TV 
     for (int e = tid; e < PER; e += 512) dst[e] = red[e];
 }
 
-static int num_cus_();
-constexpr int BP_MAXG = 512;
-static int g_bwd_pair_dma = -1;
-void debug_set_bwd_pair_dma(int mode) { g_bwd_pair_dma = mode ? 1 : 0; }
-bool bwd_pair_supported(int ks, int cin, int cout) { return ks == 3 && ((cin == 64 && cout == 32) || (cin == 32 && cout == 16)); }
+// ------------------------------------------------------------------ host side
+// Every launch below takes its kernel, tiles, G and org from a route of csrc/conv_route.hpp; nothing here decides or sizes one again.
+static long long* g_trace = nullptr;  // device buffer [1024][64] for the optional phase trace
+ConvSwitches g_conv_switches = [] {
+    ConvSwitches s;
+    const char* e = getenv("MMIF_WGRAD_TAPROW");
+    if (e != nullptr && e[0] == '0') s.wgrad_taprow = 0;
+    return s;
+}();
+static int conv_abl() {   // $MMIF_ABLATE conv= (timing ablations, diagnostics only: tools/sweep_staging.sh): bit 0 = no staging DMAs after the first chunk
+    static const int v = ablate_env("conv");
+    return v;
+}
+
 size_t bwd_pair_workspace(int cin, int cout) { return (size_t)BP_MAXG * taprow_wgrad_reduce::per(cin, cout) * sizeof(float); }
 int bwd_pair(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
              hipStream_t st) {
-    const int tiles_x = cdiv(tx.w, MT), tiles_y = cdiv(tx.h, MT);
-    const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-    const int cap = (cin == 64 ? 1 : 2) * num_cus_();
-    const int G = total < cap ? total : (cap < BP_MAXG ? cap : BP_MAXG);
-    ws = defer_ws(ws, (size_t)G * taprow_wgrad_reduce::per(cin, cout) * sizeof(float));
-    // mmif_debug_set_bwd_pair_dma(0): the register-staged kernel (the tests' cross-check; bit-identical results)
-    if (g_bwd_pair_dma < 0) g_bwd_pair_dma = 1;
-    const bool use_dma = g_bwd_pair_dma == 1 && tg.halo == 1 && tg.folded;
+    const PairRoute r = pair_route(3, cin, cout, tx, tg, cached_num_cus(), g_conv_switches);
+    if (r.kernel == PairRoute::NONE) {
+        set_error("bwd_pair: unsupported layer %d -> %d", cin, cout);
+        return MMIF_EINVAL;
+    }
+    ws = defer_ws(ws, (size_t)r.G * taprow_wgrad_reduce::per(cin, cout) * sizeof(float));
     static int bp_abl = -1;   // $MMIF_ABLATE bp= (timing ablations, wrong results): 1 no tile requests after the first, 2 no gx stores, 4 no wgrad loops, 8 no dgrad k-loops
     if (bp_abl < 0) bp_abl = ablate_env("bp");   // (the loader reads the gradient's zero ring for rows / columns past the image)
+    const bool use_dma = r.kernel == PairRoute::DMA;
     if (cin == 64 && use_dma)
-        hipLaunchKernelGGL((bwd_pair_dma_kernel<4, 2>), dim3(G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, tiles_x, tpi, total, G, bp_abl);
+        hipLaunchKernelGGL((bwd_pair_dma_kernel<4, 2>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, bp_abl);
     else if (cin == 64)
-        hipLaunchKernelGGL((bwd_pair_kernel<4, 2>), dim3(G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, tiles_x, tpi, total, G);
+        hipLaunchKernelGGL((bwd_pair_kernel<4, 2>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G);
     else if (use_dma)
-        hipLaunchKernelGGL((bwd_pair_dma_kernel<2, 1>), dim3(G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, tiles_x, tpi, total, G, bp_abl);
+        hipLaunchKernelGGL((bwd_pair_dma_kernel<2, 1>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, bp_abl);
     else
-        hipLaunchKernelGGL((bwd_pair_kernel<2, 1>), dim3(G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, tiles_x, tpi, total, G);
+        hipLaunchKernelGGL((bwd_pair_kernel<2, 1>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G);
     if (int rc = check_launch("bwd_pair")) return rc;
-    return wgrad_reduce_launch(taprow_wgrad_reduce{dw, db, cout * cin * 9, cout}, ws, G, accumulate, st);
-}
-
-// ---- backward of a WIDE 3x3 layer (Cin, Cout multiples of 64: decode.0 / decode.1) as one call: wgrad_dma_kernel also leaves the
-// ReLU sign bytes of the layer's input activations, conv_dma_kernel<true, 2> (dgrad, fused fold) reads those instead of the
-// activations themselves -- for decode.1 (128 -> 64, every input block masked) that is 0.54 of the dgrad's 1.34 GB.
-static int launch_wgrad_dma(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st, SignMap sgn);
-static int launch_conv_dma(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out, int relu,
-                           uint64_t mask_bits, uint64_t accum_bits, int org, hipStream_t st, SignMap sgn = SignMap{nullptr, 0, 0, 0},
-                           const DupOut* dup = nullptr);
-static void init_modes();
-bool bwd_wide_supported(int ks, int cin, int cout) { return ks == 3 && cin >= 64 && cout >= 64 && cin % 64 == 0 && cout % 64 == 0 && cin <= 512; }
-size_t bwd_wide_signs_bytes(int n, int cin, int h, int w) { return (size_t)n * (cin / 8) * (h + 2) * sign_pitch(w); }
-int bwd_wide(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, float* dw, float* db, int cin, int cout, uint64_t mask_bits,
-             int accumulate, float* ws, unsigned char* signs, hipStream_t st, int phase) {
-    init_modes();
-    const SignMap sgn{signs, tx.cb, tx.h + 2, sign_pitch(tx.w)};
-    if (phase != 2)   // (phase 1 / 2: only the weight-gradient / only the input-gradient half -- per-kernel timing, mmif.h)
-        if (int rc = launch_wgrad_dma(tx, tg, dw, db, cin, cout, accumulate, ws, st, mask_bits != 0 ? sgn : SignMap{nullptr, 0, 0, 0})) return rc;
-    if (phase == 1) return MMIF_OK;
-    return launch_conv_dma(true, tg, tgx, tx, wpk_dgrad, nullptr, cin, 0, mask_bits, 0, 1, st, sgn);
+    return wgrad_reduce_launch(taprow_wgrad_reduce{dw, db, cout * cin * 9, cout}, ws, r.G, accumulate, st);
 }
 
 bool conv_mfma_supported(bool dgrad, int ks, int cin, int cout) {
@@ -2346,237 +2315,132 @@ bool conv_mfma_supported(bool dgrad, int ks, int cin, int cout) {
 }
 
 template <int KS, int MF>
-static int launch_conv_mfma(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias,
+static int launch_conv_mfma(const ConvRoute& r, bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias,
                             int n_out, int relu, uint64_t mask_bits, uint64_t accum_bits, hipStream_t st) {
-    const int tiles_x = cdiv(tout.ws, MT), tiles_y = cdiv(tout.hs, MT);
     const int nmb = n_mblocks(n_out);
     const int m16p = nmb * MF * 16;
-    dim3 grid(tiles_x * tiles_y * tout.n * nmb);
     if (dgrad)
-        hipLaunchKernelGGL((conv_mfma_kernel<KS, MF, true>), grid, dim3(256), 0, st, tin, tout, tmask, (const uint4*)wpk, bias,
-                           n_out, m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, tiles_x, tiles_y, nmb, g_trace);
+        hipLaunchKernelGGL((conv_mfma_kernel<KS, MF, true>), dim3(r.G), dim3(256), 0, st, tin, tout, tmask, (const uint4*)wpk, bias,
+                           n_out, m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, nmb, g_trace);
     else
-        hipLaunchKernelGGL((conv_mfma_kernel<KS, MF, false>), grid, dim3(256), 0, st, tin, tout, tmask, (const uint4*)wpk, bias,
-                           n_out, m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, tiles_x, tiles_y, nmb, g_trace);
+        hipLaunchKernelGGL((conv_mfma_kernel<KS, MF, false>), dim3(r.G), dim3(256), 0, st, tin, tout, tmask, (const uint4*)wpk, bias,
+                           n_out, m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, nmb, g_trace);
     return check_launch(dgrad ? "conv_mfma dgrad" : "conv_mfma fwd");
 }
 
-static int num_cus_() { return cached_num_cus(); }
-
-static int g_dma_mode = 1;    // mmif_debug_set_conv_dma: 1 (default) = DMA-staged kernel where it applies, 0 = never (the tests' cross-check)
-static int g_num_cus = 0;
-constexpr int g_fuse_fold = 1;   // the DMA-staged dgrads fold the reflect halo themselves (round 2's A/B switch is gone: +5 % on the step)
-static int g_abl = 0;            // $MMIF_ABLATE conv= (diagnostics): bit 0 = no staging DMAs after the first chunk
-
-static int g_wgrad_ragged = 1;    // mmif_debug_set_ragged(0): wgrad_dma_kernel stages the padded planes of a ragged channel group too (the tests' cross-check)
-static void init_modes() {
-    static bool done = false;
-    if (done) return;
-    done = true;
-    g_abl = ablate_env("conv");      // (timing ablations, diagnostics only: tools/sweep_staging.sh)
-}
-static int launch_conv_dma(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out,
-                           int relu, uint64_t mask_bits, uint64_t accum_bits, int org, hipStream_t st, SignMap sgn, const DupOut* dup) {
+static int launch_conv_dma(const ConvRoute& r, bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out,
+                           int relu, uint64_t mask_bits, uint64_t accum_bits, hipStream_t st, SignMap sgn = SignMap{nullptr, 0, 0, 0},
+                           const DupOut* dup = nullptr) {
     DupOut dupv;
     if (dup != nullptr) dupv = *dup;
     else { dupv.out = tout; dupv.mask = tout; dupv.frag = -1; }
-    const int tiles_x = cdiv(tout.ws - 2 * org, MT), tiles_y = cdiv(tout.hs - 2 * org, DT_ROWS);
     const int nmb = n_mblocks(n_out);
     const int m16p = nmb * 4 * 16;
-    const long long nitems = (long long)tiles_x * tiles_y * tout.n * nmb;
-    g_num_cus = cached_num_cus();
-    int G = g_num_cus / 8 * 8;   // one persistent block per CU (150 KB of LDS each)
-    if (G < 8) G = 8;
-    if (nitems < G) G = (int)nitems;
-    // dgrad with ReLU masks and >= 2 chunks per tile: the loader waves stage the mask bits (-15 % on the dgrads against consumers fetching them)
-    const bool lmask = dgrad && mask_bits != 0 && cdiv(tin.cb, CHUNK_CB) >= 2;
-#define DMA_GO(D_, L_, ORG_)                                                                                                                  \
-    hipLaunchKernelGGL((conv_dma_kernel<D_, L_>), dim3(G), dim3((D_CONS + D_LOAD) * 64), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, n_out, \
-                       m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, tiles_x, tiles_y, nmb, g_trace, g_abl, ORG_, sgn, dupv)
-    if (dgrad && dupv.frag >= 0) {
-        hipLaunchKernelGGL((conv_dma_kernel<true, 0, true>), dim3(G), dim3((D_CONS + D_LOAD) * 64), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, n_out,
-                           m16p, relu, 0ull, 0ull, tiles_x, tiles_y, nmb, g_trace, g_abl, org, sgn, dupv);
-    } else if (dgrad && lmask && sgn.p != nullptr) DMA_GO(true, 2, org);
-    else if (dgrad && lmask) DMA_GO(true, 1, org);
-    else if (dgrad) DMA_GO(true, 0, org);
-    else DMA_GO(false, 0, 0);
+#define DMA_GO(D_, L_, DUP_)                                                                                                                          \
+    hipLaunchKernelGGL((conv_dma_kernel<D_, L_, DUP_>), dim3(r.G), dim3((D_CONS + D_LOAD) * 64), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, n_out, \
+                       m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, nmb, g_trace, conv_abl(), r.org, sgn, dupv)
+    if (!dgrad) DMA_GO(false, 0, false);
+    else if (r.dup) DMA_GO(true, 0, true);
+    else if (r.lmask == 2) DMA_GO(true, 2, false);
+    else if (r.lmask == 1) DMA_GO(true, 1, false);
+    else DMA_GO(true, 0, false);
 #undef DMA_GO
     return check_launch(dgrad ? "conv_dma dgrad" : "conv_dma fwd");
 }
 
+int conv1x1_stream(const ConvRoute& r, bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out,
+                   int relu, uint64_t mask_bits, hipStream_t st);   // conv1x1.hip
+
 // fold (dgrad only): the caller wants fold_halo(gx) applied as well and guarantees that gx's halo ring is zero on entry; *folded
 // reports whether the kernel chosen did it (interior tiles + fold steps, ring left zero) -- otherwise the caller runs the fold kernel.
-// the 64 -> 32 forward's geometry (thin_conv_async_kernel: two consumer groups, three tight slots of 324-granule planes)
-constexpr int TNW_GROUPS = 2, TNW_PL = 324, TNW_MAXCB = 8, TNW_MAXP = (TNW_MAXCB * TNW_PL + 63) / 64 / TN_LOAD + 1;   // 41 pieces -> 11 per loader
-constexpr int TNW_RING = 3 * ((TNW_MAXCB * TNW_PL + 63) / 64) * 1024;                                                  // 125 952 B
-static int g_thin_wide = -1;   // mmif_debug_set_thin_wide(0): decode.2's forward stays on the register-staged kernel (the tests' cross-check; bit-identical results)
-static bool thin_wide_ok(bool dgrad, int ks, int mf, const TV& tin, const TV& tout) {
-    if (g_thin_wide < 0) g_thin_wide = 1;
-    if (!(g_thin_wide == 1 && g_dma_mode == 1 && !dgrad && ks == 3 && mf == 2 && tin.cb > TN_MAXCB && tin.cb <= TNW_MAXCB && tin.plane * 16 * TNW_MAXCB < (1ll << 31)))
-        return false;
-    const long long ntiles = (long long)cdiv(tout.ws, MT) * cdiv(tout.hs, MT) * tout.n;
-    int G = num_cus_() / 8 * 8;
-    if (G < 8) G = 8;
-    return TNW_RING / (cdiv(tin.cb * TNW_PL, 64) * 1024) >= TNW_GROUPS + 1 && ntiles >= 2ll * G && ntiles < (1ll << 31);
-}
-static bool thin_async_ok(bool dgrad, int ks, int mf, const TV& tin, const TV& tout, int org) {
-    if (!(g_dma_mode == 1 && ks == 3 && mf <= 3 && (dgrad || mf >= 2) && tin.cb <= TN_MAXCB && (!dgrad || (tin.halo == 1 && tin.folded)) &&
-          tin.plane * 16 * TN_MAXCB < (1ll << 31)))
-        return false;
-    const int tiles_x = cdiv(tout.ws - 2 * org, MT), tiles_y = cdiv(tout.hs - 2 * org, MT);
-    const long long ntiles = (long long)tiles_x * tiles_y * tout.n;
-    const int P = cdiv(cdiv(tin.cb * TN_PL, 64), TN_LOAD), slot_bytes = P * TN_LOAD * 1024;
-    int G = num_cus_() / 8 * 8;
-    if (G < 8) G = 8;
-    return tn_ring_bytes(mf) / slot_bytes >= TN_GROUPS + 1 && ntiles >= 2ll * G && ntiles < (1ll << 31);
-}
-bool conv_dgrad_onto_supported(int ks, int cin, int cout, const TV& tin, const TV& tout) {
-    (void)cout;
-    init_modes();
-    const int org = (ks == 3 && g_fuse_fold == 1 && tout.halo == 1 && tout.h >= 4 && tout.w >= 4) ? 1 : 0;
-    return org == 1 && thin_async_ok(true, ks, pick_mf(cin), tin, tout, org);
-}
-
 // told (dgrad): accumulate onto THAT tensor's values instead of tout's own; only the thin asynchronous kernel implements it -- the
 // call fails (MMIF_EINVAL) when the layer / shape would take another kernel (conv_dgrad_onto_supported tells beforehand)
-bool conv_dgrad_onto_supported(int ks, int cin, int cout, const TV& tin, const TV& tout);
-bool conv1x1_stream_ok(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, int n_out, int m16p, uint64_t mask_bits, uint64_t accum_bits);   // conv1x1.hip
-int conv1x1_stream(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out, int m16p, int relu,
-                   uint64_t mask_bits, hipStream_t st);
 int conv_mfma(bool dgrad, int ks, const TV& tin, const TV& tout, const TV& tmask, const void* w_packed, const float* bias,
               int cin, int cout, int relu, uint64_t mask_bits, uint64_t accum_bits, hipStream_t st, bool fold, bool* folded, const TV* told) {
     if (folded != nullptr) *folded = false;
     const int n_out = dgrad ? cin : cout;
-    const int mf = pick_mf(n_out);
-    init_modes();
-    const int org = (dgrad && fold && folded != nullptr && ks == 3 && g_fuse_fold == 1 && tout.halo == 1 && tout.h >= 4 && tout.w >= 4) ? 1 : 0;
-    // 1x1 layers: the streaming kernel (csrc/conv1x1.hip: weights resident in LDS, B fragments straight from global memory)
-    if (ks == 1 && told == nullptr) {
-        const int m16p = n_mblocks(n_out) * mf * 16;
-        if (conv1x1_stream_ok(dgrad, tin, tout, tmask, n_out, m16p, mask_bits, accum_bits))
-            return conv1x1_stream(dgrad, tin, tout, tmask, w_packed, bias, n_out, m16p, relu, mask_bits, st);
+    const ConvRoute r = conv_route(dgrad, ks, tin, tout, n_out, mask_bits, accum_bits, fold && folded != nullptr,
+                                   told != nullptr ? ConvForm::ONTO : ConvForm::PLAIN, cached_num_cus(), g_conv_switches);
+    if (told != nullptr && r.kernel != ConvRoute::THIN_ASYNC) {
+        set_error(r.kernel == ConvRoute::CONV_DMA
+                      ? "conv dgrad: accumulate-onto-another-tensor is only implemented by the thin asynchronous kernel"
+                      : "conv dgrad: accumulate-onto-another-tensor is only implemented by the thin asynchronous kernel (this layer / shape takes another)");
+        return MMIF_EINVAL;
     }
-    // the DMA-staged kernel: 3x3, 64-row M-blocks, input gradient already folded, tensors within 32-bit plane offsets
-    if (g_dma_mode == 1 && ks == 3 && mf == 4 && (!dgrad || (tin.halo == 1 && tin.folded)) &&
-        tin.plane * 16 * CHUNK_CB < (1ll << 31))
-    {
-        if (told != nullptr) {
-            set_error("conv dgrad: accumulate-onto-another-tensor is only implemented by the thin asynchronous kernel");
-            return MMIF_EINVAL;
-        }
-        if (org) *folded = true;
-        return launch_conv_dma(dgrad, tin, tout, tmask, w_packed, bias, n_out, relu, mask_bits, accum_bits, org, st);
-    }
-    // thin layers: asynchronous loader / consumer kernel with resident weights (one M-block of <= 48 channels, <= 48 input
-    // channels, a ring of at least TN_GROUPS + 1 tile slots, at least two tiles per persistent block).  Measured (B=32 256x256,
-    // vs conv_mfma_kernel<3,MF>): every dgrad -13 .. -21 %, forward with 32 / 48 outputs -14 % / -30 %; forward with 16 outputs
-    // is +3 .. +16 % (the register-staged kernel runs 4 blocks per SIMD there), so that case stays on the old kernel.
-    if (thin_wide_ok(dgrad, ks, mf, tin, tout)) {
-        const int tiles_x = cdiv(tout.ws, MT), tiles_y = cdiv(tout.hs, MT);
-        const long long ntiles = (long long)tiles_x * tiles_y * tout.n;
-        int G = num_cus_() / 8 * 8;
-        if (G < 8) G = 8;
-        hipLaunchKernelGGL((thin_conv_async_kernel<2, false, TNW_GROUPS, TNW_PL, TNW_MAXP, TNW_RING, true>), dim3(G), dim3((4 * TNW_GROUPS + TN_LOAD) * 64), 0,
-                           st, tin, tout, tmask, (const uint4*)w_packed, bias, n_out, relu, (unsigned long long)mask_bits,
-                           (unsigned long long)accum_bits, tiles_x, tiles_y, (int)ntiles, 0, tout, 0);
-        return check_launch("thin_conv_async fwd (wide)");
-    }
-    if (thin_async_ok(dgrad, ks, mf, tin, tout, org)) {
-        const int tiles_x = cdiv(tout.ws - 2 * org, MT), tiles_y = cdiv(tout.hs - 2 * org, MT);
-        const long long ntiles = (long long)tiles_x * tiles_y * tout.n;
-        int G = num_cus_() / 8 * 8;
-        if (G < 8) G = 8;
-        {
+    if (r.org) *folded = true;
+    switch (r.kernel) {
+        case ConvRoute::CONV1X1_STREAM:
+            return conv1x1_stream(r, dgrad, tin, tout, tmask, w_packed, bias, n_out, relu, mask_bits, st);
+        case ConvRoute::CONV_DMA:
+            return launch_conv_dma(r, dgrad, tin, tout, tmask, w_packed, bias, n_out, relu, mask_bits, accum_bits, st);
+        case ConvRoute::THIN_WIDE:
+            hipLaunchKernelGGL((thin_conv_async_kernel<2, false, TNW_GROUPS, TNW_PL, TNW_MAXP, TNW_RING, true>), dim3(r.G), dim3((4 * TNW_GROUPS + TN_LOAD) * 64), 0,
+                               st, tin, tout, tmask, (const uint4*)w_packed, bias, n_out, relu, (unsigned long long)mask_bits,
+                               (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, (int)r.items, 0, tout, 0);
+            return check_launch("thin_conv_async fwd (wide)");
+        case ConvRoute::THIN_ASYNC: {
             const TV told_v = told != nullptr ? *told : tout;
             const int use_old = told != nullptr ? 1 : 0;
 #define TGO(MF_)                                                                                                                       \
     do {                                                                                                                               \
         if (dgrad)                                                                                                                     \
-            hipLaunchKernelGGL((thin_conv_async_kernel<MF_, true>), dim3(G), dim3((4 * TN_GROUPS + TN_LOAD) * 64), 0, st, tin, tout,   \
+            hipLaunchKernelGGL((thin_conv_async_kernel<MF_, true>), dim3(r.G), dim3((4 * TN_GROUPS + TN_LOAD) * 64), 0, st, tin, tout, \
                                tmask, (const uint4*)w_packed, bias, n_out, relu, (unsigned long long)mask_bits,                       \
-                               (unsigned long long)accum_bits, tiles_x, tiles_y, (int)ntiles, org, told_v, use_old);                  \
+                               (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, (int)r.items, r.org, told_v, use_old);           \
         else                                                                                                                           \
-            hipLaunchKernelGGL((thin_conv_async_kernel<MF_, false>), dim3(G), dim3((4 * TN_GROUPS + TN_LOAD) * 64), 0, st, tin, tout,  \
+            hipLaunchKernelGGL((thin_conv_async_kernel<MF_, false>), dim3(r.G), dim3((4 * TN_GROUPS + TN_LOAD) * 64), 0, st, tin, tout, \
                                tmask, (const uint4*)w_packed, bias, n_out, relu, (unsigned long long)mask_bits,                       \
-                               (unsigned long long)accum_bits, tiles_x, tiles_y, (int)ntiles, 0, told_v, 0);                          \
-        if (org) *folded = true;                                                                                                       \
+                               (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, (int)r.items, 0, told_v, 0);                     \
         return check_launch(dgrad ? "thin_conv_async dgrad" : "thin_conv_async fwd");                                                 \
     } while (0)
-            switch (mf) { case 1: TGO(1); case 2: TGO(2); default: TGO(3); }
+            switch (r.mf) { case 1: TGO(1); case 2: TGO(2); default: TGO(3); }
 #undef TGO
         }
+        default: break;
     }
-    if (told != nullptr) {
-        set_error("conv dgrad: accumulate-onto-another-tensor is only implemented by the thin asynchronous kernel (this layer / shape takes another)");
-        return MMIF_EINVAL;
-    }
-#define GO(KS_, MF_) return launch_conv_mfma<KS_, MF_>(dgrad, tin, tout, tmask, w_packed, bias, n_out, relu, mask_bits, accum_bits, st)
+#define GO(KS_, MF_) return launch_conv_mfma<KS_, MF_>(r, dgrad, tin, tout, tmask, w_packed, bias, n_out, relu, mask_bits, accum_bits, st)
     if (ks == 3) {
-        switch (mf) { case 1: GO(3, 1); case 2: GO(3, 2); case 3: GO(3, 3); default: GO(3, 4); }
+        switch (r.mf) { case 1: GO(3, 1); case 2: GO(3, 2); case 3: GO(3, 3); default: GO(3, 4); }
     } else {
-        switch (mf) { case 1: GO(1, 1); case 2: GO(1, 2); case 3: GO(1, 3); default: GO(1, 4); }
+        switch (r.mf) { case 1: GO(1, 1); case 2: GO(1, 2); case 3: GO(1, 3); default: GO(1, 4); }
     }
 #undef GO
+}
+bool conv_dgrad_onto_supported(int ks, int cin, int cout, const TV& tin, const TV& tout) {
+    (void)cout;
+    const ConvRoute r = conv_route(true, ks, tin, tout, cin, 0, 0, true, ConvForm::ONTO, cached_num_cus(), g_conv_switches);
+    return r.kernel == ConvRoute::THIN_ASYNC && r.org == 1;
 }
 
 // dgrad (folded, nothing masked or accumulated on its own output) + the two masked copies of fragment `frag` (struct DupOut): the DMA-staged
 // kernel only -- wide layers (>= 49 input channels), 3x3, the in-tile reflect fold, gy a folded halo-1 gradient
 bool conv_dgrad_dup_supported(int ks, int cin, const TV& tin, const TV& tout) {
-    init_modes();
-    return g_dma_mode == 1 && g_fuse_fold == 1 && ks == 3 && pick_mf(cin) == 4 && tin.halo == 1 && tin.folded && tout.halo == 1 && tout.h >= 4 &&
-           tout.w >= 4 && tin.plane * 16 * CHUNK_CB < (1ll << 31);
+    return conv_route(true, ks, tin, tout, cin, 0, 0, true, ConvForm::DUP, cached_num_cus(), g_conv_switches).kernel == ConvRoute::CONV_DMA;
 }
 int conv_dgrad_dup(const TV& tin, const TV& tout, const void* wpk, int cin, int cout, const TV& tdup, const TV& tmask, int frag, hipStream_t st) {
     (void)cout;
     DupOut d;
     d.out = tdup; d.mask = tmask; d.frag = frag;
-    return launch_conv_dma(true, tin, tout, tout, wpk, nullptr, cin, 0, 0, 0, 1, st, SignMap{nullptr, 0, 0, 0}, &d);
-}
-
-static inline int pick_mfw(int cout) { return cout <= 16 ? 1 : (cout <= 32 ? 2 : 4); }
-
-// tile groups per (icg, ocg) pair of the register-staged wgrad.  The grid is G * nb persistent blocks; it must fit the resident
-// capacity in ONE round (3 blocks/CU at MFW = 1 -- 136 VGPRs --, else 2; 256 CUs): 1032 blocks on 768 slots ran a second round
-// at 34 % occupancy.
-// input-channel fragments per block of the register-staged kernel: 1x1 layers with 64-row output groups take up to 4 (see the kernel)
-static inline int pick_icf(int ks, int cin, int cout) { return (ks == 1 && pick_mfw(cout) == 4) ? (cin > 32 ? 4 : (cin > 16 ? 2 : 1)) : 1; }
-
-static int wgrad_G(int cin, int cout, int icf = 1) {
-    const int mfw = pick_mfw(cout);
-    const int nb = cdiv(cin, 16 * icf) * cdiv(cout, mfw * 16);
-    const int capacity = 256 * (mfw == 1 ? 3 : 2);
-    int G = capacity / nb / 8 * 8;
-    if (G > 512) G = 512;   // (768 blocks for a single pair measured 8 % slower than 512)
-    return G < 8 ? 8 : G;
+    const ConvRoute r = conv_route(true, 3, tin, tout, cin, 0, 0, true, ConvForm::DUP, cached_num_cus(), g_conv_switches);
+    if (r.kernel != ConvRoute::CONV_DMA) {
+        set_error("conv_dgrad_dup: layer / tensors not taken by the DMA-staged dgrad");
+        return MMIF_EINVAL;
+    }
+    return launch_conv_dma(r, true, tin, tout, tout, wpk, nullptr, cin, 0, 0, 0, st, SignMap{nullptr, 0, 0, 0}, &d);
 }
 
 bool wgrad_mfma_supported(int ks, int cin, int cout) { return (ks == 1 || ks == 3) && cin >= 1 && cout >= 1; }
 
-static bool wgrad_dma_shape(int ks, int cin, int cout) {
-    const long long padded = (long long)cdiv(cin, 64) * 64 * cdiv(cout, 64) * 64;
-    return ks == 3 && cin % 8 == 0 && cout % 8 == 0 && (long long)cin * cout * 10 >= padded * 6;
-}
-static int g_wgrad_dma_blocks = 256;   // mmif_debug_set_wgrad_dma_blocks: persistent blocks of wgrad_dma_kernel (one per CU); fewer leave CUs to
-                                       // a kernel running concurrently on another stream (the intra-step overlap experiment)
-static int wgrad_dma_G(int cin, int cout, int blocks = 256) {   // tile groups per (icg, ocg) pair: about one persistent block per CU in total
-    const int npairs = cdiv(cin, 64) * cdiv(cout, 64);
-    int G = blocks / npairs;
-    if (G >= 8) G = G / 8 * 8;   // multiples of 8 keep the blocks that share tiles on one XCD
-    return G < 1 ? 1 : G;
-}
-
 // enc_wgrad.hip: single-layer "tap-row" kernel (whole x / g tile staged once per block)
-bool wgrad_taprow_supported(int ks, int cin, int cout);
 size_t wgrad_taprow_workspace(int cin, int cout);
-int wgrad_taprow(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st);
-static int g_taprow_mode = -1;   // $MMIF_WGRAD_TAPROW=0: keep the per-input-group kernel (A/B timing)
+int wgrad_taprow(const WgradRoute& r, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st);
 
 size_t wgrad_mfma_workspace(int cin, int cout, int ks) {
     const int mfw = pick_mfw(cout), icf = pick_icf(ks, cin, cout);
     size_t a = 0;
     for (int f = 1; f <= icf; f *= 2) {   // (either block width may run)
         const size_t per = grouped_per(16 * f, mfw * 16, ks * ks);      // wgrad_mfma_reduce<ks, mfw, f>::PER
-        const size_t b = (size_t)wgrad_G(cin, cout, f) * cdiv(cin, 16 * f) * cdiv(cout, mfw * 16) * per * sizeof(float);
+        const size_t b = (size_t)wgrad_mfma_G(cin, cout, f) * cdiv(cin, 16 * f) * cdiv(cout, mfw * 16) * per * sizeof(float);
         if (b > a) a = b;
     }
     if (wgrad_dma_shape(ks, cin, cout)) {
@@ -2590,63 +2454,61 @@ size_t wgrad_mfma_workspace(int cin, int cout, int ks) {
     return a;
 }
 
-static int launch_wgrad_dma(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st,
-                            SignMap sgn = SignMap{nullptr, 0, 0, 0}) {
-    const int tiles_x = cdiv(tx.w, MT), tiles_y = cdiv(tx.h, MT);
-    const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-    const int n_icg = cdiv(cin, 64), n_ocg = cdiv(cout, 64);
-    int G = wgrad_dma_G(cin, cout, g_wgrad_dma_blocks);   // (the workspace is sized for the full grid)
-    if (G > total) G = total;   // every tile group owns at least one tile (the reduce sums all G partials)
-    ws = defer_ws(ws, (size_t)G * n_icg * n_ocg * WD_PER * sizeof(float));      // (csrc/wgrad_reduce.hpp: an arena slot while reductions are deferred)
-    hipLaunchKernelGGL(wgrad_dma_kernel, dim3(G * n_icg * n_ocg), dim3((D_CONS + D_LOAD) * 64), 0, st, tx, tg, ws, tiles_x, tpi, total, G,
-                       n_icg, n_ocg, sgn, g_wgrad_ragged);
+static int launch_wgrad_dma(const WgradRoute& r, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
+                            hipStream_t st, SignMap sgn = SignMap{nullptr, 0, 0, 0}) {
+    ws = defer_ws(ws, (size_t)r.G * r.n_icg * r.n_ocg * WD_PER * sizeof(float));      // (csrc/wgrad_reduce.hpp: an arena slot while reductions are deferred)
+    hipLaunchKernelGGL(wgrad_dma_kernel, dim3(r.G * r.n_icg * r.n_ocg), dim3((D_CONS + D_LOAD) * 64), 0, st, tx, tg, ws, r.tiles_x, r.tpi, r.total, r.G,
+                       r.n_icg, r.n_ocg, sgn, g_conv_switches.wgrad_ragged);
     if (int rc = check_launch("wgrad_dma")) return rc;
-    return wgrad_reduce_launch(wgrad_dma_reduce{{dw, db, cin, cout, n_icg, n_ocg}}, ws, G, accumulate, st);
+    return wgrad_reduce_launch(wgrad_dma_reduce{{dw, db, cin, cout, r.n_icg, r.n_ocg}}, ws, r.G, accumulate, st);
 }
 
-template <int KS, int MFW, int KSPLIT, int ICF = 1>
-static int launch_wgrad_mfma(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
+template <int KS, int MFW, int KSPLIT, int ICF>
+static int launch_wgrad_mfma(const WgradRoute& r, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
                              hipStream_t st) {
-    const int tiles_x = cdiv(tx.w, MT), tiles_y = cdiv(tx.h, MT);
-    const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-    int G = wgrad_G(cin, cout, ICF);
-    if (G > total) G = total;  // (no longer a multiple of 8: the kernel falls back to the plain block order)
-    const int n_icg = cdiv(cin, 16 * ICF), n_ocg = cdiv(cout, MFW * 16);
-    hipLaunchKernelGGL((wgrad_mfma_kernel<KS, MFW, KSPLIT, ICF>), dim3(G * n_icg * n_ocg), dim3(256), 0, st, tx, tg, ws, tiles_x, tpi,
-                       total, G, n_icg, n_ocg);
+    hipLaunchKernelGGL((wgrad_mfma_kernel<KS, MFW, KSPLIT, ICF>), dim3(r.G * r.n_icg * r.n_ocg), dim3(256), 0, st, tx, tg, ws, r.tiles_x, r.tpi,
+                       r.total, r.G, r.n_icg, r.n_ocg);
     if (int rc = check_launch("wgrad_mfma")) return rc;
-    return wgrad_reduce_launch(wgrad_mfma_reduce<KS, MFW, ICF>{{dw, db, cin, cout, n_icg, n_ocg}}, ws, G, accumulate, st);
+    return wgrad_reduce_launch(wgrad_mfma_reduce<KS, MFW, ICF>{{dw, db, cin, cout, r.n_icg, r.n_ocg}}, ws, r.G, accumulate, st);
 }
 
 int wgrad_mfma(int ks, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws,
                hipStream_t st) {
-    const int mfw = pick_mfw(cout);
-    init_modes();
-    if (g_dma_mode == 1 && wgrad_dma_shape(ks, cin, cout) && tg.halo == 1 && tg.folded && tx.plane * 16 * 8 < (1ll << 31) &&
-        tg.plane * 16 * 8 < (1ll << 31))
-        return launch_wgrad_dma(tx, tg, dw, db, cin, cout, accumulate, ws, st);
-    if (g_taprow_mode < 0) {
-        const char* e = getenv("MMIF_WGRAD_TAPROW");
-        g_taprow_mode = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    if (g_taprow_mode == 1 && wgrad_taprow_supported(ks, cin, cout) && (tg.halo == 0 || tg.folded) && tx.halo == 0)
-        return wgrad_taprow(tx, tg, dw, db, cin, cout, accumulate, ws, st);
-#define GO(KS_, M_, K_) return launch_wgrad_mfma<KS_, M_, K_>(tx, tg, dw, db, cin, cout, accumulate, ws, st)
+    const WgradRoute r = wgrad_route(ks, cin, cout, tx, tg, cached_num_cus(), g_conv_switches);
+    if (r.kernel == WgradRoute::DMA) return launch_wgrad_dma(r, tx, tg, dw, db, cin, cout, accumulate, ws, st);
+    if (r.kernel == WgradRoute::TAPROW) return wgrad_taprow(r, tx, tg, dw, db, cin, cout, accumulate, ws, st);
+#define GO(KS_, M_, K_, I_) return launch_wgrad_mfma<KS_, M_, K_, I_>(r, tx, tg, dw, db, cin, cout, accumulate, ws, st)
     if (ks == 3) {
-        switch (mfw) { case 1: GO(3, 1, 4); case 2: GO(3, 2, 2); default: GO(3, 4, 2); }
+        switch (r.mfw) { case 1: GO(3, 1, 4, 1); case 2: GO(3, 2, 2, 1); default: GO(3, 4, 2, 1); }
     } else {
-        switch (mfw) {
-            case 1: GO(1, 1, 4);
-            case 2: GO(1, 2, 2);
+        switch (r.mfw) {
+            case 1: GO(1, 1, 4, 1);
+            case 2: GO(1, 2, 2, 1);
             default:
-                switch (pick_icf(1, cin, cout)) {
-                    case 4: return launch_wgrad_mfma<1, 4, 2, 4>(tx, tg, dw, db, cin, cout, accumulate, ws, st);
-                    case 2: return launch_wgrad_mfma<1, 4, 2, 2>(tx, tg, dw, db, cin, cout, accumulate, ws, st);
-                    default: GO(1, 4, 2);
-                }
+                switch (r.icf) { case 4: GO(1, 4, 2, 4); case 2: GO(1, 4, 2, 2); default: GO(1, 4, 2, 1); }
         }
     }
 #undef GO
+}
+
+// ---- backward of a WIDE 3x3 layer (Cin, Cout multiples of 64: decode.0 / decode.1) as one call: wgrad_dma_kernel also leaves the
+// ReLU sign bytes of the layer's input activations, conv_dma_kernel<true, 2> (dgrad, fused fold) reads those instead of the
+// activations themselves -- for decode.1 (128 -> 64, every input block masked) that is 0.54 of the dgrad's 1.34 GB.
+bool bwd_wide_supported(int ks, int cin, int cout) { return ks == 3 && cin >= 64 && cout >= 64 && cin % 64 == 0 && cout % 64 == 0 && cin <= 512; }
+size_t bwd_wide_signs_bytes(int n, int cin, int h, int w) { return (size_t)n * (cin / 8) * (h + 2) * sign_pitch(w); }
+int bwd_wide(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, float* dw, float* db, int cin, int cout, uint64_t mask_bits,
+             int accumulate, float* ws, unsigned char* signs, hipStream_t st, int phase) {
+    const SignMap sgn{signs, tx.cb, tx.h + 2, sign_pitch(tx.w)};
+    const WgradRoute wr = wgrad_route(3, cin, cout, tx, tg, cached_num_cus(), g_conv_switches, true);
+    const ConvRoute r = conv_route(true, 3, tg, tgx, cin, mask_bits, 0, true, ConvForm::WIDE_SIGNS, cached_num_cus(), g_conv_switches);
+    if (wr.kernel != WgradRoute::DMA || r.kernel != ConvRoute::CONV_DMA) {
+        set_error("bwd_wide: layer %d -> %d / tensors not taken by the DMA-staged kernels", cin, cout);
+        return MMIF_EINVAL;
+    }
+    if (phase != 2)   // (phase 1 / 2: only the weight-gradient / only the input-gradient half -- per-kernel timing, mmif.h)
+        if (int rc = launch_wgrad_dma(wr, tx, tg, dw, db, cin, cout, accumulate, ws, st, mask_bits != 0 ? sgn : SignMap{nullptr, 0, 0, 0})) return rc;
+    if (phase == 1) return MMIF_OK;
+    return launch_conv_dma(r, true, tg, tgx, tx, wpk_dgrad, nullptr, cin, 0, mask_bits, 0, st, sgn);
 }
 
 }  // namespace mmif
@@ -2655,11 +2517,12 @@ using namespace mmif;
 
 extern "C" void mmif_debug_set_trace(void* device_buf) { mmif::g_trace = (long long*)device_buf; }
 // 1 (default) = use the DMA-staged kernels where they apply, 0 = register-staged kernels only
-extern "C" void mmif_debug_set_conv_dma(int32_t mode) { mmif::g_dma_mode = mode ? 1 : 0; }
-extern "C" void mmif_debug_set_bwd_pair_dma(int32_t mode) { mmif::debug_set_bwd_pair_dma(mode); }
-extern "C" void mmif_debug_set_thin_wide(int32_t mode) { mmif::g_thin_wide = mode ? 1 : 0; }
-extern "C" void mmif_debug_set_ragged(int32_t mode) { mmif::g_wgrad_ragged = mode ? 1 : 0; }
-extern "C" void mmif_debug_set_wgrad_dma_blocks(int32_t blocks) { mmif::g_wgrad_dma_blocks = blocks < 8 ? 8 : (blocks > 256 ? 256 : blocks); }
+extern "C" void mmif_debug_set_conv_dma(int32_t mode) { g_conv_switches.conv_dma = mode ? 1 : 0; }
+extern "C" void mmif_debug_set_conv1x1_stream(int32_t mode) { g_conv_switches.conv1x1_stream = mode ? 1 : 0; }
+extern "C" void mmif_debug_set_bwd_pair_dma(int32_t mode) { g_conv_switches.bwd_pair_dma = mode ? 1 : 0; }
+extern "C" void mmif_debug_set_thin_wide(int32_t mode) { g_conv_switches.thin_wide = mode ? 1 : 0; }
+extern "C" void mmif_debug_set_ragged(int32_t mode) { g_conv_switches.wgrad_ragged = mode ? 1 : 0; }
+extern "C" void mmif_debug_set_wgrad_dma_blocks(int32_t blocks) { g_conv_switches.wgrad_dma_blocks = blocks < 8 ? 8 : (blocks > 256 ? 256 : blocks); }
 
 extern "C" size_t mmif_packed_weight_bytes(int32_t cout, int32_t cin, int32_t ksize) {
     const size_t a = packed_bytes(cout, cin, ksize), b = packed_bytes(cin, cout, ksize);

@@ -13,6 +13,7 @@
 //           N = 9 taps + a column of ones = db0) and db1..db3 (bf16 MFMA against ones)
 // No K split between waves -> no cross-wave reduction; per-block partials are reduced in a fixed order by a second kernel
 // (deterministic, no atomics).  ~250 B staged per pixel => HBM-bound; 2 blocks per CU (65 KB LDS each).
+#include "conv_route.hpp"
 #include "enc_wgrad.hpp"
 
 namespace mmif {
@@ -373,17 +374,11 @@ __global__ __launch_bounds__(256, 2) void taprow_wgrad_kernel(TV tx, TV tg, floa
     for (int e = tid; e < PER; e += 256) dst[e] = red[e];
 }
 
-bool wgrad_taprow_supported(int ks, int cin, int cout) {
-    if (ks != 3 || cin % 16 || cout % 16) return false;
-    const int nxb = cin / 16, ngb = cout / 16;
-    return (ngb == 1 && nxb >= 1 && nxb <= 3) || (ngb == 2 && (nxb == 2 || nxb == 4));
-}
 size_t wgrad_taprow_workspace(int cin, int cout) { return (size_t)EW_MAXG * taprow_wgrad_reduce::per(cin, cout) * sizeof(float); }
 
-int wgrad_taprow(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st) {
-    const int tiles_x = cdiv(tx.w, EW_T), tiles_y = cdiv(tx.h, EW_T);
-    const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-    const int G = total < EW_MAXG ? total : EW_MAXG;
+// the layers it takes and its grid: wgrad_route(), csrc/conv_route.hpp
+int wgrad_taprow(const WgradRoute& r, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st) {
+    const int tiles_x = r.tiles_x, tpi = r.tpi, total = r.total, G = r.G;
     const int nxb = cin / 16, ngb = cout / 16;
 #define GO(X_, G_) hipLaunchKernelGGL((taprow_wgrad_kernel<X_, G_>), dim3(G), dim3(256), 0, st, tx, tg, ws, tiles_x, tpi, total, G)
     if (ngb == 1) { switch (nxb) { case 1: GO(1, 1); break; case 2: GO(2, 1); break; default: GO(3, 1); break; } }

@@ -44,6 +44,13 @@ int validate_tensor(const mmif_tensor* t, const char* name) {
         set_error("%s: null tensor", name);
         return MMIF_EINVAL;
     }
+    return validate_extent(t, name);
+}
+int validate_extent(const mmif_tensor* t, const char* name) {
+    if (t == nullptr) {
+        set_error("%s: null tensor", name);
+        return MMIF_EINVAL;
+    }
     if (t->dtype != MMIF_F32 && t->dtype != MMIF_BF16) {
         set_error("%s: bad dtype %d", name, t->dtype);
         return MMIF_EINVAL;

@@ -314,9 +314,11 @@ bool defer_push(const RedJob& job);
 // dW / db of map m = fixed-order sum of the G partials at `partial` (accumulate: onto what is there); queued instead while reductions are
 // deferred and `partial` is the arena slot defer_ws() handed out last
 template <class Map>
+constexpr int red_slices(int G) { return (Map::SL == 0 ? G > 64 : Map::SL == 16) ? 16 : 4; }   // the map's slice rule
+template <class Map>
 int wgrad_reduce_launch(const Map& m, const float* partial, int G, int accumulate, hipStream_t st) {
     const int nvb = cdiv(m.n(), 64);
-    const bool wide = Map::SL == 0 ? G > 64 : Map::SL == 16;
+    const bool wide = red_slices<Map>(G) == 16;
     if constexpr (red_deferrable<Map>) {
         RedJob J;
         J.partial = partial; J.sl = wide ? 16 : 4; J.G = G; J.accumulate = accumulate; J.nvb = nvb;

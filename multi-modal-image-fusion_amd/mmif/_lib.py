@@ -39,6 +39,13 @@ class MmifDenseChain(C.Structure):
                 ("out", C.POINTER(MmifTensor))]
 
 
+class MmifRoute(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("G", C.c_int32), ("slices", C.c_int32), ("tiles", C.c_int32), ("org", C.c_int32)]
+
+
+ROUTE_OPS = {"fwd": 0, "dgrad": 1, "dgrad_onto": 2, "dgrad_dup": 3, "wgrad": 4, "bwd_pair": 5, "bwd_wide": 6}
+
+
 class MmifError(RuntimeError):
     pass
 
@@ -136,6 +143,7 @@ SIGNATURES = {
     "mmif_conv2d_dgrad_onto_supported": (_i32, [_TP, _TP, _i32, _i32, _i32]),
     "mmif_conv2d_reflect_dgrad_folded_onto": (_i32, [_TP, _vp, _TP, _TP, _TP, _i32, _i32, _i32, _u64, _u64, _vp]),
     "mmif_conv2d_reflect_dgrad_folded": (_i32, [_TP, _vp, _vp, _TP, _TP, _i32, _i32, _i32, _u64, _u64, _i32, _vp]),
+    "mmif_conv2d_route": (_i32, [_i32, _TP, _TP, _i32, _i32, _i32, _u64, _u64, _i32, _i32, _i32, C.POINTER(MmifRoute)]),
     "mmif_conv2d_wgrad_workspace": (_sz, [_i32, _i32, _i32]),
     "mmif_conv2d_reflect_wgrad": (_i32, [_TP, _TP, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
     "mmif_conv2d_image_in_fwd": (_i32, [_vp, _vp, _vp, _TP, _i32, _i32, _i32, _vp]),

@@ -453,22 +453,22 @@ class ModelEngine:
         return T.conv_dgrad(gy, s.w.detach(), x, gx, s.cin, s.cout, s.k, mask_bits, accum_bits, s.packed, impl, s.name + ":dgrad", fold=True)
 
     @staticmethod
-    def pair_ok(s, dtype, impl, h, w):
-        """this layer's backward runs as ONE launch (csrc/conv_mfma.hip bwd_pair_kernel; $MMIF_BWD_PAIR=0: dgrad and wgrad apart)"""
-        return (dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and not s.split and s.relu and s.packed is not None and h >= 4 and w >= 4
-                and T.bwd_pair_supported(s.cin, s.cout, s.k) and switch("MMIF_BWD_PAIR"))
+    def pair_ok(s, dtype, impl, x, gy):
+        """this layer's backward runs as ONE launch (csrc/conv_mfma.hip bwd_pair_kernel; $MMIF_BWD_PAIR=0: dgrad and wgrad apart); the
+        layer and shape limits are the library's own (mmif_conv2d_route: what the call would refuse is not taken)"""
+        return (dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and not s.split and s.relu and s.packed is not None
+                and switch("MMIF_BWD_PAIR") and T.conv_route("bwd_pair", x, gy, s.cin, s.cout, s.k) is not None)
 
     @staticmethod
-    def wide_ok(s, dtype, impl, x, gx):
+    def wide_ok(s, dtype, impl, x, gy, gx):
         """this layer's backward runs as wgrad (leaving ReLU sign bytes) + dgrad reading them (csrc/conv_mfma.hip bwd_wide;
         $MMIF_BWD_WIDE=0: the two calls apart, the dgrad reading the activations)"""
         if dtype == torch.float32:   # split-operand kernels (csrc/conv_x3.hip): any layer they take; the map is 1/32 of the bytes of x
             return (impl != _lib.IMPL_VALU and x3_enabled() and not s.split and s.packed is not None and s.packed.fmt == _lib.F32
                     and x.halo == 0 and gx.halo == 1 and x.cb == (s.cin + 7) // 8 and gx.cb == x.cb and x.h >= 2 and x.w >= 2
                     and T.bwd_wide_supported(s.cin, s.cout, s.k, dtype) and switch("MMIF_BWD_WIDE"))
-        return (dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and not s.split and s.packed is not None and x.h >= 4 and x.w >= 4
-                and x.halo == 0 and gx.halo == 1 and x.cb * 8 == s.cin and T.bwd_wide_supported(s.cin, s.cout, s.k)
-                and (x.h + 2) * (x.w + 2) * 128 < (1 << 31) and switch("MMIF_BWD_WIDE"))
+        return (dtype == torch.bfloat16 and impl != _lib.IMPL_VALU and not s.split and s.packed is not None and gx.halo == 1
+                and switch("MMIF_BWD_WIDE") and T.conv_route("bwd_wide", x, gy, s.cin, s.cout, s.k) is not None)
 
     def c_bwd_wide(self, s, gy, x, gx, mask_bits, ws):
         need = T.bwd_wide_signs_bytes(x.n, s.cin, x.h, x.w)
@@ -763,7 +763,7 @@ class DenseEncoderMixin:
             for i in range(len(self.dec) - 2, -1, -1):
                 s, x = self.dec[i], acts[i]
                 gx = self.buf(L, f"G{i}", n, s.cin, h, w, dtype, dev, halo=1)
-                if i > 0 and self.pair_ok(s, dtype, impl, h, w):
+                if i > 0 and self.pair_ok(s, dtype, impl, x, g):
                     g = self.c_bwd_pair(s, g, x, gx, ws)      # thin layer: dgrad (every block masked) + wgrad in one launch
                     continue
                 if i == 0 and dup is not None:
@@ -772,7 +772,7 @@ class DenseEncoderMixin:
                         g, dup_ran = gd, True
                         continue
                 mb = all_bits(gx.cb) if i > 0 else mask0
-                if self.wide_ok(s, dtype, impl, x, gx):
+                if self.wide_ok(s, dtype, impl, x, g, gx):
                     g = self.c_bwd_wide(s, g, x, gx, mb, ws)  # wide layer: the wgrad leaves the ReLU sign bytes the dgrad masks with
                     continue
                 self.c_wgrad(s, x, g, ws, impl)

@@ -1,5 +1,6 @@
 """Blocked-NHWC device tensors and thin wrappers over the C ABI (one Python call = one kernel launch
 sequence on the current HIP stream)."""
+import collections
 import ctypes as C
 
 import torch
@@ -220,6 +221,20 @@ def conv_dgrad_onto(gy, x, gx_old, gx, cin, cout, k, mask_bits, accum_bits, pack
         check(lib.mmif_conv2d_reflect_dgrad_folded_onto(gy.d, _ptr(packed.dgrad), x.d if x is not None else None, gx_old.d, gx.d, cin, cout, k,
                                                         mask_bits, accum_bits, stream_ptr()), "conv2d_reflect_dgrad_folded_onto")
     return gx.as_folded()
+
+
+Route = collections.namedtuple("Route", "name G slices tiles org")
+
+
+def conv_route(op, a, b, cin, cout, k, mask_bits=0, accum_bits=0, fold=False, impl=_lib.IMPL_AUTO, num_cus=0):
+    """the kernel the call `op` ('fwd', 'dgrad', 'dgrad_onto', 'dgrad_dup', 'wgrad', 'bwd_pair', 'bwd_wide') would launch on the descriptors
+    a, b (mmif.h: mmif_conv2d_route; BT tensors or MmifTensor structs, whose data is never read) and its grid, or None where the call would
+    refuse; num_cus = 0: the current device's"""
+    r = _lib.MmifRoute()
+    a, b = (getattr(t, "d", t) for t in (a, b))
+    if not lib.mmif_conv2d_route(_lib.ROUTE_OPS[op], a, b, cin, cout, k, mask_bits, accum_bits, int(fold), impl, num_cus, r):
+        return None
+    return Route(r.name.decode(), r.G, r.slices, r.tiles, r.org)
 
 
 def conv_wgrad(x, gy, dw, db, cin, cout, k, ws, accumulate=False, impl=_lib.IMPL_AUTO, tag=None):

@@ -1,6 +1,7 @@
-"""Cases, fp64 definitions and a restatement of the kernel dispatch for the generic 3x3 / 1x1 ConvLayer kernels (csrc/conv_mfma.hip,
-csrc/conv_x3.hip, csrc/conv_valu.hip, csrc/conv1x1.hip; dispatch in csrc/conv_api.hip).  No GPU needed: tests/test_conv_oracle_cpu.py pins the
-definitions to torch's float64 autograd and the case list to the dispatch; tests/test_gpu_conv_sweep.py runs every case on the device.
+"""Cases and fp64 definitions for the generic 3x3 / 1x1 ConvLayer kernels (csrc/conv_mfma.hip, csrc/conv_x3.hip, csrc/conv_valu.hip,
+csrc/conv1x1.hip; dispatch in csrc/conv_route.hpp and csrc/conv_api.hip), and the library's own answer to "which kernel does this call
+launch" (mmif_conv2d_route).  No GPU needed: tests/test_conv_oracle_cpu.py pins the definitions to torch's float64 autograd and the case list
+to the dispatch; tests/test_gpu_conv_sweep.py runs every case on the device.
 
 The definitions (all float64, on oracle.fusion_oracle):
 
@@ -38,30 +39,14 @@ def cdiv(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# the dispatch, restated from conv_mfma() / wgrad_mfma() / launch_conv_dma() (csrc/conv_mfma.hip) and pick_impl() (csrc/conv_api.hip)
+# the dispatch, ASKED: mmif_conv2d_route (csrc/conv_api.hip) answers from the route functions the launches themselves go through
+# (csrc/conv_route.hpp), on descriptors without data -- no GPU needed when num_cus is given
 # ------------------------------------------------------------------------------------------------------------------------------
-MT, DT_ROWS, CHUNK_CB = 16, 32, 4
-TN_MAXCB, TN_PL, TN_GROUPS, TN_LOAD = 6, 336, 3, 4
-TNW_GROUPS, TNW_PL, TNW_MAXCB = 2, 324, 8
-TNW_RING = 3 * cdiv(TNW_MAXCB * TNW_PL, 64) * 1024
-C1_MAX_LDS = 128 * 1024
 DEFAULT_SWITCHES = {"conv_dma": 1, "thin_wide": 1, "conv1x1_stream": 1, "wgrad_dma_blocks": 256}     # the mmif_debug_set_* switches
 
 
 def pick_mf(n_out):
     return min(cdiv(n_out, 16), 4)
-
-
-def n_mblocks(n_out):
-    return cdiv(cdiv(n_out, 16), pick_mf(n_out))
-
-
-def tn_ring_bytes(mf):
-    return {1: 128, 2: 112}.get(mf, 96) * 1024
-
-
-def persistent_grid(num_cus):
-    return max(num_cus // 8 * 8, 8)
 
 
 def pick_mfw(cout):
@@ -72,111 +57,51 @@ def pick_icf(ks, cin, cout):
     return (4 if cin > 32 else (2 if cin > 16 else 1)) if (ks == 1 and pick_mfw(cout) == 4) else 1
 
 
-def wgrad_dma_shape(ks, cin, cout):
-    padded = cdiv(cin, 64) * 64 * cdiv(cout, 64) * 64
-    return ks == 3 and cin % 8 == 0 and cout % 8 == 0 and cin * cout * 10 >= padded * 6
+class switches:
+    """the library's mmif_debug_set_* switches set to sw inside the block, back to their defaults after it"""
+
+    def __init__(self, sw):
+        self.sw = sw
+
+    def _set(self, values):
+        from mmif._lib import lib
+        for k in self.sw:
+            getattr(lib, "mmif_debug_set_" + k)(values[k])
+
+    def __enter__(self):
+        self._set(self.sw)
+
+    def __exit__(self, *a):
+        self._set(DEFAULT_SWITCHES)
 
 
-def wgrad_taprow_supported(ks, cin, cout):
-    if ks != 3 or cin % 16 or cout % 16:
-        return False
-    nxb, ngb = cin // 16, cout // 16
-    return (ngb == 1 and 1 <= nxb <= 3) or (ngb == 2 and nxb in (2, 4))
+def route(op, dtype, cin, cout, n, h, w, gy_folded=True, fold=False, mask_bits=0, accum_bits=0, num_cus=256, switches_=None, k=3, impl="auto",
+          gy_halo=1, gx_halo=1):
+    """What the library launches for the call (mmif.tensor.conv_route: name, G, slices, tiles, org), None where it would refuse.  op: 'fwd',
+    'dgrad' (fold = the folded call), 'dgrad_onto', 'dgrad_dup', 'wgrad', 'bwd_pair', 'bwd_wide'.  dtype 'bf16' / 'f32'; impl 'auto' / 'mfma' /
+    'x3' / 'valu'; num_cus = 0: the current device's."""
+    from mmif import _lib as L
+    from mmif import tensor as T
 
-
-def wgrad_dma_G(cin, cout, blocks=256):
-    G = blocks // (cdiv(cin, 64) * cdiv(cout, 64))
-    if G >= 8:
-        G = G // 8 * 8
-    return max(G, 1)
-
-
-def wgrad_G(cin, cout, icf=1):
-    mfw = pick_mfw(cout)
-    nb = cdiv(cin, 16 * icf) * cdiv(cout, mfw * 16)
-    G = min((256 * (3 if mfw == 1 else 2)) // nb // 8 * 8, 512)
-    return max(G, 8)
-
-
-def thin_async_ok(dgrad, ks, mf, in_cb, in_halo, in_folded, in_plane, out_hs, out_ws, n, org, num_cus, sw):
-    if not (sw["conv_dma"] == 1 and ks == 3 and mf <= 3 and (dgrad or mf >= 2) and in_cb <= TN_MAXCB
-            and (not dgrad or (in_halo == 1 and in_folded)) and in_plane * 16 * TN_MAXCB < (1 << 31)):
-        return False
-    ntiles = cdiv(out_ws - 2 * org, MT) * cdiv(out_hs - 2 * org, MT) * n
-    slot_bytes = cdiv(cdiv(in_cb * TN_PL, 64), TN_LOAD) * TN_LOAD * 1024
-    return tn_ring_bytes(mf) // slot_bytes >= TN_GROUPS + 1 and 2 * persistent_grid(num_cus) <= ntiles < (1 << 31)
-
-
-def thin_wide_ok(dgrad, ks, mf, in_cb, in_plane, out_hs, out_ws, n, num_cus, sw):
-    if not (sw["thin_wide"] == 1 and sw["conv_dma"] == 1 and not dgrad and ks == 3 and mf == 2 and TN_MAXCB < in_cb <= TNW_MAXCB
-            and in_plane * 16 * TNW_MAXCB < (1 << 31)):
-        return False
-    ntiles = cdiv(out_ws, MT) * cdiv(out_hs, MT) * n
-    return TNW_RING // (cdiv(in_cb * TNW_PL, 64) * 1024) >= TNW_GROUPS + 1 and 2 * persistent_grid(num_cus) <= ntiles < (1 << 31)
-
-
-def conv1x1_stream_ok(sw, in_hs, in_ws, out_hs, out_ws, in_halo, in_folded, in_cb, n_out, m16p, accum_bits):
-    if sw["conv1x1_stream"] == 0 or accum_bits != 0:
-        return False
-    if (in_hs, in_ws) != (out_hs, out_ws) or (in_halo != 0 and not in_folded):
-        return False
-    if m16p > 256 or m16p % 16 or n_out > m16p:
-        return False
-    return cdiv(in_cb, 4) * 4 * m16p * 16 + m16p * 4 <= C1_MAX_LDS
+    def t(c, halo, folded=False):
+        return L.MmifTensor(None, L.BF16 if dtype == "bf16" else L.F32, n, h, w, halo, cdiv(c, 8), 0, cdiv(c, 8), L.T_FOLDED if (halo and folded) else 0)
+    if op == "fwd":
+        a, b = t(cin, 0), t(cout, 0)
+    elif op.startswith("dgrad"):
+        a, b = t(cout, gy_halo, gy_folded), t(cin, gx_halo)
+    else:
+        a, b = t(cin, 0), t(cout, gy_halo, gy_folded)
+    code = {"auto": L.IMPL_AUTO, "mfma": L.IMPL_MFMA, "x3": L.IMPL_X3, "valu": L.IMPL_VALU}[impl]
+    with switches(switches_ or {}):
+        return T.conv_route(op, a, b, cin, cout, k, mask_bits, accum_bits, fold, code, num_cus)
 
 
 def expected_kernel(op, dtype, cin, cout, n, h, w, gy_folded=True, fold=False, mask_bits=0, accum_bits=0, num_cus=256, switches=None, k=3,
                     impl="auto", gy_halo=1, gx_halo=1):
-    """Name of the kernel the library launches.  op: 'fwd', 'dgrad' (fold = the folded call; '_onto' has the same dispatch), 'wgrad',
-    'bwd_pair', 'bwd_wide' (the input-gradient half; its weight-gradient half is always wgrad_dma), 'dgrad_dup'.  dtype 'bf16' / 'f32';
-    impl 'auto' / 'mfma' / 'x3' / 'valu' (pick_impl: fp32 tensors never reach the bf16 kernels; 'auto' on fp32 takes x3 when the operand image
-    is given, which the cases always do)."""
-    sw = dict(DEFAULT_SWITCHES, **(switches or {}))
-    if dtype == "f32":
-        return "valu" if impl == "valu" else "x3"
-    if impl == "valu":
-        return "valu"
-    if op == "bwd_pair":
-        return "bwd_pair"
-    if op == "wgrad":
-        mfw = pick_mfw(cout)
-        if sw["conv_dma"] == 1 and wgrad_dma_shape(k, cin, cout) and gy_halo == 1 and gy_folded:
-            return "wgrad_dma"
-        if wgrad_taprow_supported(k, cin, cout) and (gy_halo == 0 or gy_folded):
-            return "wgrad_taprow"
-        if k == 3:
-            return f"wgrad_mfma<3,{mfw}>"
-        return f"wgrad_mfma<1,{mfw},2,{pick_icf(1, cin, cout)}>" if mfw == 4 else f"wgrad_mfma<1,{mfw}>"
-    dgrad = op != "fwd"
-    n_out = cin if dgrad else cout
-    n_in = cout if dgrad else cin
-    mf = pick_mf(n_out)
-    in_cb = cdiv(n_in, 8)
-    in_halo = gy_halo if dgrad else 0
-    in_folded = gy_folded if dgrad else False
-    in_hs, in_ws = h + 2 * in_halo, w + 2 * in_halo
-    out_halo = gx_halo if dgrad else 0
-    out_hs, out_ws = h + 2 * out_halo, w + 2 * out_halo
-    if op == "bwd_wide":
-        lmask = mask_bits != 0 and cdiv(in_cb, CHUNK_CB) >= 2
-        return f"conv_dma<L{2 if lmask else 0},org1>"
-    if op == "dgrad_dup":
-        return "conv_dma<L0,org1,dup>"
-    org = 1 if (dgrad and fold and k == 3 and out_halo == 1 and h >= 4 and w >= 4) else 0
-    if k == 1:
-        m16p = n_mblocks(n_out) * mf * 16
-        if conv1x1_stream_ok(sw, in_hs, in_ws, out_hs, out_ws, in_halo, in_folded, in_cb, n_out, m16p, accum_bits):
-            return "conv1x1_stream"
-    if sw["conv_dma"] == 1 and k == 3 and mf == 4 and (not dgrad or (in_halo == 1 and in_folded)) and in_hs * in_ws * 16 * CHUNK_CB < (1 << 31):
-        if not dgrad:
-            return "conv_dma<L0,org0>"
-        lmask = mask_bits != 0 and cdiv(in_cb, CHUNK_CB) >= 2
-        return f"conv_dma<L{1 if lmask else 0},org{org}>"
-    if thin_wide_ok(dgrad, k, mf, in_cb, in_hs * in_ws, out_hs, out_ws, n, num_cus, sw):
-        return "thin_wide"
-    if thin_async_ok(dgrad, k, mf, in_cb, in_halo, in_folded, in_hs * in_ws, out_hs, out_ws, n, org, num_cus, sw):
-        return f"thin_async<{mf}>"
-    return f"mfma<{k},{mf}>"
+    """Name of the kernel the library launches ('none': it would refuse the call); for 'bwd_wide' the input-gradient half (its
+    weight-gradient half is always wgrad_dma)."""
+    r = route(op, dtype, cin, cout, n, h, w, gy_folded, fold, mask_bits, accum_bits, num_cus, switches, k, impl, gy_halo, gx_halo)
+    return r.name if r is not None else "none"
 
 
 # every kernel name the sweep must reach (tests/test_conv_oracle_cpu.py fails on an unreached one)
@@ -228,11 +153,16 @@ class Case:
     def sw(self):
         return dict(self.switches)
 
-    def expected(self, num_cus=256, mask_bits=None, accum_bits=None):
+    def route(self, num_cus=256, mask_bits=None, accum_bits=None):
+        """what the library launches for this case under its switches (see route())"""
         m, a = self.bits[0] if mask_bits is None else (mask_bits, accum_bits)
         cbm = (1 << cdiv(self.cin, 8)) - 1
-        return expected_kernel("dgrad" if self.op == "dgrad_onto" else self.op, self.dtype, self.cin, self.cout, self.n, self.h, self.w,
-                               self.gy_folded, self.fold, m & cbm, a & cbm, num_cus, self.sw, self.k, self.impl, self.gy_halo, self.gx_halo)
+        return route(self.op, self.dtype, self.cin, self.cout, self.n, self.h, self.w, self.gy_folded, self.fold, m & cbm, a & cbm, num_cus, self.sw,
+                     self.k, self.impl, self.gy_halo, self.gx_halo)
+
+    def expected(self, num_cus=256, mask_bits=None, accum_bits=None):
+        r = self.route(num_cus, mask_bits, accum_bits)
+        return r.name if r is not None else "none"
 
 
 NO_DMA = (("conv_dma", 0),)

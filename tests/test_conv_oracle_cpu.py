@@ -1,5 +1,6 @@
-"""tests/conv_cases.py without a GPU: its fp64 definitions against torch's float64 autograd and golden F3, its case list against its
-restatement of the dispatch (every kernel name reached), and the non-vacuity of every case's reference."""
+"""tests/conv_cases.py without a GPU: its fp64 definitions against torch's float64 autograd and golden F3, its case list against the
+library's dispatch (mmif_conv2d_route on descriptors without data: every kernel name reached, the thresholds between kernels), and the
+non-vacuity of every case's reference."""
 import dataclasses
 import os
 
@@ -108,7 +109,7 @@ def test_definitions_equal_golden_f3(case):
 
 
 def test_every_case_reaches_its_kernel_and_every_kernel_is_reached():
-    """at 256 compute units expected_kernel gives each case's label for every bit pair it runs; every required name has a case"""
+    """at 256 compute units the library's dispatch gives each case's label for every bit pair it runs; every required name has a case"""
     wrong = [(c.id, m, a, c.expected(256, m, a)) for c in CASES for m, a in c.bits if c.expected(256, m, a) != c.label]
     assert not wrong, wrong[:10]
     reached = {c.label for c in CASES}
@@ -125,6 +126,32 @@ def test_tile_thresholds_of_the_asynchronous_kernel():
     assert ek("dgrad", "bf16", 16, 16, 3, 180, 200, fold=True, num_cus=128) == "thin_async<1>"
     assert ek("fwd", "bf16", 16, 48, 3, 178, 190) == "mfma<3,3>" and ek("fwd", "bf16", 16, 48, 3, 208, 224) == "thin_async<3>"
     assert ek("fwd", "bf16", 16, 16, 3, 208, 224) == "mfma<3,1>", "16 outputs forward stays on the register-staged kernel"
+
+
+@pytest.mark.parametrize("cin,cout,k,h,w,fast,slow", [
+    (8, 64, 3, 4096, 8191, "conv_dma<L0,org0>", "mfma<3,4>"),            # plane * 16 * CHUNK_CB: 2^25 granules per plane is the first too many
+    (40, 24, 3, 2, 11184810, "thin_async<2>", "mfma<3,2>"),              # plane * 16 * TN_MAXCB: 22 369 621 is the last plane that fits
+    (64, 32, 3, 2048, 8191, "thin_wide", "mfma<3,2>"),                   # plane * 16 * TNW_MAXCB: 2^24
+    (8, 64, 1, 8192, 16383, "conv1x1_stream", "mfma<1,4>"),              # the 1x1 kernel's plane * 16: 2^27
+], ids=["conv_dma", "thin_async", "thin_wide", "conv1x1_stream"])
+def test_32_bit_plane_limits_of_the_fast_kernels(cin, cout, k, h, w, fast, slow):
+    """a forward whose input plane is the last that keeps the kernel's 32-bit byte offsets takes the fast kernel; one more column of
+    pixels (the first plane at or past the limit) falls back to the register-staged kernel.  Geometry only: no memory behind it."""
+    per_plane = {"conv_dma<L0,org0>": 16 * 4, "thin_async<2>": 16 * 6, "thin_wide": 16 * 8, "conv1x1_stream": 16}[fast]
+    assert h * w * per_plane < (1 << 31) <= h * (w + 1) * per_plane
+    assert CC.expected_kernel("fwd", "bf16", cin, cout, 1, h, w, k=k) == fast
+    assert CC.expected_kernel("fwd", "bf16", cin, cout, 1, h, w + 1, k=k) == slow
+
+
+@pytest.mark.parametrize("num_cus", [8, 256])
+def test_two_tiles_per_persistent_block_is_the_threshold(num_cus):
+    """the asynchronous kernels (both geometries) want 2 G tiles, G = the compute units rounded down to a multiple of 8: 2 G - 1 tiles stay
+    on the register-staged kernel, 2 G and 2 G + 1 leave it"""
+    G = num_cus // 8 * 8
+    for cin, cout, fast in ((40, 24, "thin_async<2>"), (64, 32, "thin_wide")):
+        got = [CC.route("fwd", "bf16", cin, cout, n, 16, 16, num_cus=num_cus) for n in (2 * G - 1, 2 * G, 2 * G + 1)]
+        assert [r.name for r in got] == ["mfma<3,2>", fast, fast], (num_cus, cin, cout, got)
+        assert [r.tiles for r in got] == [2 * G - 1, 2 * G, 2 * G + 1] and [r.G for r in got] == [2 * G - 1, G, G]
 
 
 @pytest.mark.parametrize("c", [_small(c) for c in CASES], ids=lambda c: c.id)

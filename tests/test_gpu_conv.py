@@ -72,7 +72,7 @@ DMA_SHAPES = [(128, 128, 2, 37, 53), (176, 112, 1, 64, 48), (72, 64, 2, 33, 40),
 # 48 -> 48 (six input channel blocks leave the three-fragment kernel's ring fewer than four tile slots)
 DMA_SHAPES += [(16, 16, 3, 180, 200), (16, 48, 3, 178, 190), (48, 48, 2, 241, 275)]
 # thin layers (<= 48 channels either side) take the asynchronous loader/consumer kernel once a persistent block owns at least
-# two tiles: >= 512 tiles of 16x16 on a 256-CU part (asserted through conv_cases.expected_kernel below)
+# two tiles: >= 512 tiles of 16x16 on a 256-CU part (asserted through the library's route query below)
 THIN_ASYNC_SHAPES = [(48, 16, 2, 250, 270), (32, 16, 2, 256, 256), (24, 40, 2, 257, 300), (8, 16, 2, 256, 300),
                      (16, 16, 3, 208, 224), (16, 48, 3, 208, 224)]
 DMA_SHAPES += THIN_ASYNC_SHAPES
@@ -96,8 +96,8 @@ def test_dma_staged_kernels_equal_register_staged(cin, cout, n, h, w):
     dev = "cuda:0"
     if (cin, cout, n, h, w) in THIN_ASYNC_SHAPES:   # the folded gy of this test: forward by Cout, the padded-domain dgrad by Cin
         ncu = torch.cuda.get_device_properties(0).multi_processor_count
-        took = (expected_kernel("fwd", "bf16", cin, cout, n, h, w, num_cus=ncu), expected_kernel("dgrad", "bf16", cin, cout, n, h, w, True, False,
-                                                                                                   1, 1, ncu))
+        took = (expected_kernel("fwd", "bf16", cin, cout, n, h, w, num_cus=0), expected_kernel("dgrad", "bf16", cin, cout, n, h, w, True, False,
+                                                                                                 1, 1, 0))      # 0: asked of the library for this device
         assert any(t.startswith("thin_async") for t in took), f"listed as a thin asynchronous shape, but mode 1 takes {took} with {ncu} compute units"
     torch.manual_seed(cin * 7 + cout)
     x = T.BT.alloc(n, cin, h, w, torch.bfloat16, dev); x.buf.normal_()

@@ -1,7 +1,7 @@
 """Every kernel path of the generic 3x3 / 1x1 ConvLayer against its fp64 definition (tests/conv_cases.py), element-wise, with derived bounds.
 
-Each case first proves where it goes: conv_cases.expected_kernel -- the dispatch restated in Python -- must give the case's label for the
-device's compute-unit count (a mismatch fails, it never skips).  Outputs are pre-filled with a sentinel; nothing outside the written view
+Each case first proves where it goes: the library's own dispatch, asked through mmif_conv2d_route for the device's compute-unit count
+(conv_cases.route), must give the case's label (a mismatch fails, it never skips).  Outputs are pre-filled with a sentinel; nothing outside the written view
 may change (neighbouring channel blocks of a wider buffer, the zero ring of a folded gradient).
 
 Bounds.  bf16 outputs, per element (conv_cases.bf16_bound):  |got - ref| <= 2^-8 A + (K + 2) 2^-24 S.
@@ -100,22 +100,7 @@ def _check_dw(c, family, dw, db, accumulate, bar):
             _check_norm(c, family + " tap", dw[:, :, u, v], dw_ref[:, :, u, v], bar, f"dw[{u}][{v}] acc={accumulate}")
 
 
-class _switches:
-    SET = {"conv_dma": "mmif_debug_set_conv_dma", "thin_wide": "mmif_debug_set_thin_wide", "conv1x1_stream": "mmif_debug_set_conv1x1_stream",
-           "wgrad_dma_blocks": "mmif_debug_set_wgrad_dma_blocks"}
-
-    def __init__(self, sw):
-        self.sw = sw
-
-    def __enter__(self):
-        from mmif._lib import lib
-        for k, v in self.sw.items():
-            getattr(lib, self.SET[k])(v)
-
-    def __exit__(self, *a):
-        from mmif._lib import lib
-        for k in self.sw:
-            getattr(lib, self.SET[k])(CC.DEFAULT_SWITCHES[k])
+_switches = CC.switches
 
 
 def _setup(c):
@@ -139,8 +124,14 @@ def _num_cus():
 
 def _assert_route(c, m=None, a=None):
     ncu = _num_cus()
-    got = c.expected(ncu, m, a)
+    got = c.expected(0, m, a)          # 0: the compute units the library's launches count
     assert got == c.label, f"{c.id}: meant for {c.label}, but with {ncu} compute units the dispatch takes {got}"
+
+
+def _onto_route(c, m, a):
+    """the accumulate-onto form of the case's call is taken (by the thin asynchronous kernel, folding in its tiles), switches at their defaults"""
+    r = dataclasses.replace(c, op="dgrad_onto", switches=()).route(0, m, a)
+    return r is not None and r.name.startswith("thin_async") and r.org == 1
 
 
 def _fp32_bar(c):
@@ -219,10 +210,11 @@ def test_input_gradient_equals_definition(c):
             fresh = CC.ring_zero(np.full(old.shape, 5.0))        # the previous contents of gx itself must not enter
             gx, gxwhole = _bt(fresh, c.cin, c.h, c.w, hx, _td(c), slot)
             assert T.dgrad_onto_supported(gy, gx, c.cin, c.cout, c.k), f"{c.id}: the library declines the accumulate-onto form here"
+            assert _onto_route(c, m, a), f"{c.id}: dgrad_onto_supported disagrees with the route query"
         elif c.label.startswith("thin_async") and c.fold:
-            assert T.dgrad_onto_supported(gy, gx, c.cin, c.cout, c.k), f"{c.id}: dgrad_onto_supported disagrees with expected_kernel"
+            assert T.dgrad_onto_supported(gy, gx, c.cin, c.cout, c.k) and _onto_route(c, m, a), f"{c.id}: dgrad_onto_supported disagrees with the route query"
         elif c.label.startswith("mfma<3") and c.fold and c.dtype == "bf16" and not c.sw and c.gy_folded and c.gy_halo:
-            assert not T.dgrad_onto_supported(gy, gx, c.cin, c.cout, c.k), f"{c.id}: dgrad_onto_supported disagrees with expected_kernel"
+            assert not T.dgrad_onto_supported(gy, gx, c.cin, c.cout, c.k) and not _onto_route(c, m, a), f"{c.id}: dgrad_onto_supported disagrees with the route query"
         with _switches(c.sw):
             if onto:
                 T.conv_dgrad_onto(gy, x if m else None, gold, gx, c.cin, c.cout, c.k, m, a, pk)

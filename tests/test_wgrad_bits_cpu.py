@@ -35,9 +35,13 @@ def test_db_not_wanted_is_covered_per_entry_point():
 
 
 def test_G_follows_the_launchers_formulas():
-    """spot values worked by hand from the launchers (16 x 16 tiles unless said)"""
+    """spot values worked by hand from the launchers (16 x 16 tiles unless said); the ConvLayer calls' pin what the library answers"""
     assert B.G_dma(64, 64, 3, 80, 96) == 90 and B.G_dma(64, 136, 3, 80, 96) == 80 and B.G_dma(64, 64, 2, 33, 40) == 18
     assert B.G_mfma(20, 12, 3, 1, 33, 40) == 9 and B.G_mfma(88, 64, 1, 2, 33, 40) == 18
+    assert B.G_taprow(48, 16, 2, 33, 40) == 18 and B.G_taprow(48, 16, 3, 80, 96) == 90 and B.G_pair(64, 3, 80, 96) == 90
+    assert B.G_dma(64, 64, 9, 128, 128) == 256 and B.G_mfma(20, 12, 3, 9, 128, 128) == 384 and B.G_pair(32, 9, 128, 128) == 512     # the caps
+    import conv_cases as CC
+    assert CC.route("bwd_pair", "bf16", 32, 16, 2, 256, 257, num_cus=304).G == 512, "544 tiles on 304 compute units: the workspace holds 512 partials"
     assert B.G_x3(64, 64, 3, 2, 40, 96) == 60 and B.G_x3(72, 40, 1, 1, 80, 48) == 90          # 8 x 16 tiles; 1x1: three partials per block
     assert B.G_x3_thin(48, 3, 40, 96) == 90 and B.G_x3_dense(2, 33, 40) == 30
     assert B.G_image(3, 80, 96) == 90 and B.G_image(2, 33, 40) == 11                          # 256 pixels per block
@@ -57,7 +61,8 @@ def test_fixture_holds_exactly_the_table():
 
 
 def test_conv_wgrad_cases_take_the_route_their_flavour_names():
-    """conv_cases.expected_kernel -- the dispatch restated in Python -- for every conv_wgrad case of the table"""
+    """the library's dispatch (conv_cases.expected_kernel asks mmif_conv2d_route) for every conv_wgrad case of the table, and the slice
+    count of its reduce"""
     import conv_cases as CC
     want = {"wgrad_dma_reduce": "wgrad_dma", "taprow_wgrad_reduce": "wgrad_taprow", "wgrad_x3_reduce": "x3", "wgrad_x3_thin_reduce": "x3"}
     routes = set()
@@ -71,6 +76,9 @@ def test_conv_wgrad_cases_take_the_route_their_flavour_names():
             assert route == (f"wgrad_mfma<3,{mfw}>" if ks == "3" else f"wgrad_mfma<1,{mfw},2,{icf}>"), (c.id, route)
         else:
             assert route == want[flavour], (c.id, route)
+        if c.dtype == "bf16":
+            r = CC.route("wgrad", c.dtype, c.cin, c.cout, c.n, c.h, c.w, k=c.k, impl="mfma", num_cus=B.NUM_CUS)
+            assert (r.G, r.slices) == c.reduces[0][1:], (c.id, r)
         if flavour == "wgrad_x3_thin_reduce":
             assert c.cin <= 48 and c.cout <= 16 and c.k == 3, c.id
         routes.add(route)

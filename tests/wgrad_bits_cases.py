@@ -12,8 +12,9 @@ tail):
     main+tail   G > 4 SL and G mod 4 SL != 0    main loop, then a tail of another length in some slices
 The flavours whose SL follows G (wgrad_dma, wgrad_x3: SL = 16 if G > 64 else 4) cannot reach `tail` at SL 16 (G > 64 > 48).
 
-G is not exported: each case's G below is derived from its launcher's formula (for 256 compute units where the formula has them; the
-shapes here keep G = the tile count, below every such cap) and checked by tests/test_wgrad_bits_cpu.py.  Shapes are the smallest that
+The ConvLayer calls' G comes from the library (mmif_conv2d_route at 256 compute units: the route the launch itself takes); the x3, image
+and encoder kernels' G is not exported and is derived below from their launchers' formulas (for 256 compute units where the formula has
+them; the shapes here keep G = the tile count, below every such cap).  tests/test_wgrad_bits_cpu.py checks both.  Shapes are the smallest that
 reach the regime: 16 x 16-tile producers run 2 x 33 x 40 (18 tiles), 1 x 33 x 40 (9) and 3 x 80 x 96 (90).
 """
 from __future__ import annotations
@@ -45,20 +46,27 @@ def sl_by_G(G):
     return 16 if G > 64 else 4
 
 
+def _G(op, kernel, cin, cout, k, n, h, w):
+    """G of the library's route for the call, which must be the kernel the caller means"""
+    r = CC.route(op, "bf16", cin, cout, n, h, w, k=k, impl="mfma", num_cus=NUM_CUS)
+    assert r is not None and r.name.startswith(kernel), (op, kernel, cin, cout, k, n, h, w, r)
+    return r.G
+
+
 def G_dma(cin, cout, n, h, w):
-    return min(CC.wgrad_dma_G(cin, cout), tiles(n, h, w, 16, 16))
+    return _G("wgrad", "wgrad_dma", cin, cout, 3, n, h, w)
 
 
 def G_mfma(cin, cout, k, n, h, w):
-    return min(CC.wgrad_G(cin, cout, CC.pick_icf(k, cin, cout)), tiles(n, h, w, 16, 16))
+    return _G("wgrad", "wgrad_mfma", cin, cout, k, n, h, w)
 
 
-def G_taprow(n, h, w):
-    return min(tiles(n, h, w, 16, 16), 512)
+def G_taprow(cin, cout, n, h, w):
+    return _G("wgrad", "wgrad_taprow", cin, cout, 3, n, h, w)
 
 
 def G_pair(cin, n, h, w):
-    return min(tiles(n, h, w, 16, 16), min((1 if cin == 64 else 2) * NUM_CUS, 512))
+    return _G("bwd_pair", "bwd_pair", cin, cin // 2, 3, n, h, w)
 
 
 def G_x3(cin, cout, k, n, h, w):
@@ -178,7 +186,7 @@ def _cases():
             return ((f"wgrad_x3_reduce<taps {k * k}>/{sl_by_G(G)}", G, sl_by_G(G)),)
         return f
 
-    taprow = lambda n, h, w: (("taprow_wgrad_reduce/16", G_taprow(n, h, w), 16),)
+    taprow = lambda n, h, w: (("taprow_wgrad_reduce/16", G_taprow(48, 16, n, h, w), 16),)
     # ---- conv_wgrad, bf16
     _variants(cs, "wgrad", dma(64, 64), [S9, S18, S90], cin=64, cout=64)                     # SL 4 tail, SL 4 main+tail, SL 16
     _variants(cs, "wgrad", dma(64, 136), [S90], cin=64, cout=136, note="ragged")             # 3 output groups: G = 80, SL 16
