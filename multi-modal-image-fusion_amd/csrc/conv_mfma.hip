@@ -742,8 +742,7 @@ __device__ inline void dgrad_fold_steps(f32x4 (&acc)[MF][4], const char* in_c, c
 
 constexpr int D_CONS = 8;                                          // consumer waves (MFMA): wave w owns tile rows 4w..4w+3
 constexpr int D_LOAD = 4;                                          // loader waves (LDS-DMA issue only), one per SIMD
-constexpr int DL_ITERS = (D_PIECES + D_LOAD - 1) / D_LOAD;         // 19 pieces per loader wave per chunk
-constexpr int DL_IN_ITERS = (DIN_PIECES + D_LOAD - 1) / D_LOAD;    // 10 of them may be input pieces
+constexpr int DL_IN_ITERS = (DIN_PIECES + D_LOAD - 1) / D_LOAD;    // input pieces per loader wave per chunk: 10 (9 on the last wave)
 
 // ReLU sign bytes of an activation tensor, in the PADDED domain of its gradient: [n][cb][hs = h + 2][pitch] bytes, bit i of the byte
 // at (row Y, column X) = channel 8 cb + i of image pixel (Y - 1, X - 1) is > 0.  The byte of column X lives at X + SIGN_XOFF, so that
@@ -759,16 +758,32 @@ static inline int sign_pitch(int w) { return (cdiv(w, MT) + 2) * MT; }
 // (LMASK: 0 = none, 1 = the loaders reduce the mask ACTIVATIONS to sign bytes, 2 = they fetch ready sign bytes -- struct SignMap)
 // (DUP: the dgrad that also leaves struct DupOut's masked copies -- its own instantiation: as a run-time option of <true, 0> the extra
 // operands spilled 28 registers at the 168-register budget)
-template <bool DGRAD, int LMASK, bool DUP = false>
+// (DIAG: the instantiation the diagnostics run -- the s_memtime stamps of tools/trace_dma.py / conv_clock.py and the $MMIF_ABLATE conv=
+// timing ablations.  The shipped form has neither the arguments nor a test of them: the stamps cost ~300 cycles per chunk and `tr`, a
+// 64-bit lane register, in a kernel at its register ceiling.  The host launches DIAG only when a trace buffer or an ablation is set.)
+template <bool DIAG> struct DiagArgs {};
+template <> struct DiagArgs<true> {
+    long long* trace;
+    int abl;
+};
+template <bool DGRAD, int LMASK, bool DUP = false, bool DIAG = false>
 __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV tin, TV tout, TV tmask, const uint4* __restrict__ wpk,
                                                                               const float* __restrict__ bias, int n_out, int m16p, int relu,
                                                                               unsigned long long mask_bits, unsigned long long accum_bits,
-                                                                              int tiles_x, int tiles_y, int nmb, long long* __restrict__ trace,
-                                                                              int abl, int org, SignMap sgn, DupOut dup) {
+                                                                              int tiles_x, int tiles_y, int nmb, int org, SignMap sgn, DupOut dup,
+                                                                              DiagArgs<DIAG> diag) {
     constexpr int MF = 4;
+    long long* trace = nullptr;   // constants in the shipped form: every test of them below folds away
+    int abl = 0;
+    if constexpr (DIAG) { trace = diag.trace; abl = diag.abl; }
     __shared__ __attribute__((aligned(16))) char s_buf[2 * DBUF_BYTES];
     __shared__ int2 s_tab[2][DW_PIECES];
     __shared__ __attribute__((aligned(16))) float s_bias[3][MF * 16];
+    // the items {mb, in_, tile_y, tile_x} the loaders have decoded, a ring of three rotated like s_bias: slot i % 3 is written by loader
+    // wave 0 before it arrives at the barrier that opens item i's first chunk and read by the consumers after that barrier -- the
+    // consumers run none of decode()'s five divisions by run-time divisors (they sat on the critical path of waves 4..7, which arrive
+    // at the barrier last)
+    __shared__ __attribute__((aligned(16))) int4 s_item[3];
     // dgrad: ReLU-mask sign bits of two tiles in flight ([item parity][channel block of the M-block][tile row][tile col], one byte =
     // 8 channels).  The consumers' epilogue used to fetch the mask activations itself -- 8 global round trips on the critical path of
     // every tile, and all of a tile's k-loop is only 2 chunks for a 64-channel input (decode.1's dgrad).  The LOADER waves have the
@@ -808,16 +823,21 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
     }
     if (count == 0) return;
     auto decode = [&](int lin) {
+        // (unsigned: every operand is non-negative, and a signed division by a run-time divisor carries its sign fix-ups -- and their
+        // scalar registers -- across the chunk loop)
         DItem it;
-        it.mb = lin % nmb;
-        const int tl = lin / nmb;
-        it.in_ = tl / tpi;
-        const int trem = tl - it.in_ * tpi;
-        it.tile_y = trem / tiles_x;
-        it.tile_x = trem - it.tile_y * tiles_x;
+        const unsigned ul = (unsigned)lin, unmb = (unsigned)nmb, utpi = (unsigned)tpi, utx = (unsigned)tiles_x;
+        const unsigned tl = ul / unmb;
+        it.mb = (int)(ul - tl * unmb);
+        const unsigned uin = tl / utpi, trem = tl - uin * utpi;
+        const unsigned ty = trem / utx;
+        unsigned txx = trem - ty * utx;
         // fused fold: a block's items are a whole number of tile rows apart, so without a skew one block would own ONLY left-border
         // tiles (three extra k-steps per chunk each) and set the kernel's makespan; rotate the columns by row and image
-        if (org) it.tile_x = (it.tile_x + it.tile_y + it.in_) % tiles_x;
+        if (org) txx = (txx + ty + uin) % utx;
+        it.in_ = (int)uin;
+        it.tile_y = (int)ty;
+        it.tile_x = (int)txx;
         return it;
     };
     const int ncb_tot = tin.cb;
@@ -875,6 +895,11 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
         // dgrad, DenseFuse's decode.0) whose block keeps one M-block finds its weights where the last item left them and does not request
         // them again (36 of a chunk's 75 pieces)
         int wres[2] = {-1, -1};
+        static_assert(DIN_PIECES == D_LOAD * (DL_IN_ITERS - 1) + D_LOAD - 1 && DW_PIECES % D_LOAD == 0 && D_PIECES == DIN_PIECES + DW_PIECES,
+                      "piece split of issue_dma");
+        const int kgf = (lw + 1) & (D_LOAD - 1);                       // this wave's first weight plane (piece 39 + kgf = lw mod 4)
+        const unsigned wstep = (unsigned)m16p * 16u;                   // bytes per k-group plane of the packed image
+        const unsigned w_off0 = (unsigned)lane * 16u + (unsigned)kgf * wstep;
         auto issue_dma = [&](const DItem& itm, int c, int buf, int item_no = 0) {
             // timing ablations (results are garbage): $MMIF_ABLATE conv= bit 1 = no WEIGHT pieces on every second item (what a weight chunk
             // shared by two pixel tiles could save at most), bit 3 = no INPUT pieces on every second item (an input tile shared by two M-blocks)
@@ -883,32 +908,48 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
             wres[buf] = wkey;
             const int ncb = min(CHUNK_CB, ncb_tot - c * CHUNK_CB);
             const int nkgp = (9 * ncb + 3) / 4 * 4;
-            char* dst_in = s_buf + buf * DBUF_BYTES;
-            char* dst_w = dst_in + CHUNK_CB * DPL * 16;
+            // Piece P = lw + 4 i of the chunk's 75 is input piece P (P < 39) or weight plane P - 39.  Taken per wave that is: input pieces
+            // lw + 4 i for i < 9 (+ piece 36 + lw for the waves lw < 3) and the NINE weight planes kgf + 4 k, kgf = (lw + 1) & 3 -- so the
+            // only wave-dependent test left is one.  Per piece the wave issues the load, one M0 write and one offset add; nothing per piece
+            // is a loop-invariant scalar that has to live across the chunk loop (the 64-bit `kg * m16p * 16` and range predicates of a
+            // piece-indexed loop were: 135 spilled SGPRs, five v_readlane per piece between two loads).
+            char* dst_in = s_buf + buf * DBUF_BYTES + lw * 1024;
+            char* dst_w = s_buf + buf * DBUF_BYTES + CHUNK_CB * DPL * 16 + kgf * 1024;
             const char* src_in = tin.base + ((long long)itm.in_ * tin.img + (long long)(tin.cb_off + c * CHUNK_CB) * tin.plane) * 16;
-            const char* src_w = reinterpret_cast<const char*>(wpk) + ((long long)c * DW_PIECES * m16p + itm.mb * MF * 16 + lane) * 16;
+            const char* src_w = reinterpret_cast<const char*>(wpk) + ((long long)c * DW_PIECES * m16p + itm.mb * MF * 16) * 16;
+            auto pieces = [&](auto full_c) {
+                constexpr bool FULL = decltype(full_c)::value != 0;   // a full chunk: no ragged plane fix-up, all 36 weight planes
+                if (!skip_in) {
 #pragma unroll
-            for (int i = 0; i < DL_ITERS; ++i) {
-                const int P = lw + D_LOAD * i;   // wave-uniform piece index
-                if (i < DL_IN_ITERS && P < DIN_PIECES) {
-                    unsigned off = d_off[i < DL_IN_ITERS ? i : 0];
-                    if (ncb != CHUNK_CB) {   // ragged last chunk (wave uniform): planes past the end re-read the last valid one
-                        const unsigned cb = (d_cb >> (2 * (i < DL_IN_ITERS ? i : 0))) & 3u;
-                        off -= (cb - min(cb, (unsigned)(ncb - 1))) * plane_bytes;
+                    for (int i = 0; i < DL_IN_ITERS; ++i) {
+                        if (i == DL_IN_ITERS - 1 && lw + D_LOAD * i >= DIN_PIECES) break;   // wave uniform: piece 39 is not an input piece
+                        unsigned off = d_off[i];
+                        if (!FULL) {   // ragged last chunk: planes past the end re-read the last valid one
+                            const unsigned cb = (d_cb >> (2 * i)) & 3u;
+                            off -= (cb - min(cb, (unsigned)(ncb - 1))) * plane_bytes;
+                        }
+                        __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_in + off), MMIF_LPTR(dst_in + i * (D_LOAD * 1024)), 16, 0, 0);
                     }
-                    if (!skip_in) __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_in + off), MMIF_LPTR(dst_in + P * 1024), 16, 0, 0);
-                } else if (P >= DIN_PIECES && P < D_PIECES) {
-                    const int kg = P - DIN_PIECES;
-                    if (kg < nkgp && !skip_w)
-                        __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_w + (long long)kg * m16p * 16), MMIF_LPTR(dst_w + kg * 1024), 16, 0, 0);
                 }
-            }
+                if (!skip_w) {
+                    unsigned woff = w_off0;   // lane * 16 + kgf * wstep
+                    const int wlim = nkgp - kgf;
+#pragma unroll
+                    for (int k = 0; k < DW_PIECES / D_LOAD; ++k) {
+                        if (FULL || D_LOAD * k < wlim)   // (against a constant: kgf + 4 k itself would be nine scalars held across the loop)
+                            __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_w + woff), MMIF_LPTR(dst_w + k * (D_LOAD * 1024)), 16, 0, 0);
+                        woff += D_LOAD * wstep;
+                    }
+                }
+            };
+            if (ncb == CHUNK_CB) pieces(IC<1>());
+            else pieces(IC<0>());
         };
         auto load_bias = [&](const DItem& itm, int slot) {
-            const int t = tid - D_CONS * 64;
-            if (!DGRAD && t < MF * 16) {
-                const int oc = itm.mb * MF * 16 + t;
-                s_bias[slot][t] = (bias != nullptr && oc < n_out) ? bias[oc] : 0.f;
+            static_assert(MF * 16 == 64, "the M-block's bias is one wave's worth");
+            if (!DGRAD && lw == 0) {   // (a scalar test: no lane mask to hold across the chunk loop)
+                const int oc = itm.mb * MF * 16 + lane;
+                s_bias[slot][lane] = (bias != nullptr && oc < n_out) ? bias[oc] : 0.f;
             }
         };
         // ---- mask bits: thread t of the 256 loader threads owns tile pixels t and t + 256 of every channel block of the M-block
@@ -967,7 +1008,14 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
                 }
             }
         };
+        auto publish = [&](const DItem& itm, int slot) {
+            if (lw == 0) {   // (every lane stores the same four scalars: a scalar test, no lane mask to hold across the chunk loop)
+                s_item[slot] = make_int4(itm.mb, itm.in_, itm.tile_y, itm.tile_x);
+                __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // performed before this wave arrives at the next barrier
+            }
+        };
         DItem cur = decode(first), mitem = cur;
+        publish(cur, 0);
         make_desc(cur);
         load_bias(cur, 0);
         issue_dma(cur, 0, 0);
@@ -986,6 +1034,7 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
                 ++item_i;
                 if (q + 1 < total_q) {
                     cur = decode(first + item_i * stride);
+                    publish(cur, item_i % 3);
                     make_desc(cur);
                     load_bias(cur, item_i % 3);
                 }
@@ -1019,7 +1068,9 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
                                                 accum_bits, tout.ws - org, tout.hs - org, nullptr, wave * 4 + (g & 1), j, nullptr, &dup);     \
         }                                                                                                                                     \
     } while (0)
-    DItem cur = decode(first), pend = cur;
+    DItem cur = {0, 0, 0, 0}, pend = cur;
+    // (A static s_setprio 1 for waves 4..7 here, no per-step flips, was measured: forward 399.0 -> 394.8 us, dgrad 416.4 -> 418.8 us per
+    // launch, the step 3.557 -> 3.544 ms with a spread of 0.05 ms -- not told from noise, not kept.)
     bool have_pend = false;
     int pend_slot = 0, pend_par = 0;
     int c = 0, item_i = 0;
@@ -1033,6 +1084,13 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
         int lane_q;
         __asm__ volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_q));
         const int j = lane_q & 15, g = lane_q >> 4;
+        if (c == 0) {   // a new item: its slot of the ring is visible since this barrier (requested here, awaited behind the pending epilogue)
+            const int4 it4 = s_item[item_i % 3];
+            cur.mb = __builtin_amdgcn_readfirstlane(it4.x);
+            cur.in_ = __builtin_amdgcn_readfirstlane(it4.y);
+            cur.tile_y = __builtin_amdgcn_readfirstlane(it4.z);
+            cur.tile_x = __builtin_amdgcn_readfirstlane(it4.w);
+        }
         if (have_pend) {   // waves 4..7: previous tile's outputs, stored under the partner wave's MFMAs (see below)
             __builtin_amdgcn_s_setprio(3);   // (measured neutral; the epilogue is ~180 VALU instructions either way)
             DMA_EPILOGUE(pend, pend_slot, pend_par);
@@ -1040,18 +1098,20 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
             have_pend = false;
         }
         DTRACE();   // pending epilogue done
-        if (c == 0) {
-#pragma unroll
-            for (int m = 0; m < MF; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
         const int ncb = min(CHUNK_CB, ncb_tot - c * CHUNK_CB);
         const char* in_lane = s_buf + buf * DBUF_BYTES + ((wave * 4) * DTP_X + j) * 16;
         const char* w_lane = s_buf + buf * DBUF_BYTES + CHUNK_CB * DPL * 16 + j * 16;
         // a wave whose 4 rows lie below the output (ragged last tile row; 258 = 8*32 + 2 for the padded domain of a 256-row
         // dgrad) has nothing to compute: it leaves the MFMA pipe to its SIMD partner and just keeps the barrier count
         const bool rows_live = !DGRAD || org + cur.tile_y * DT_ROWS + wave * 4 < tout.hs - org;
+        // (The first k-step of an item with a literal zero C operand instead of this clear -- a second copy of the k-loop below chosen by
+        // c == 0 -- was built and dropped: at the 168-register budget the copy spilled 20 (forward) / 90 (dgrad) vector registers.)
+        if (c == 0) {
+#pragma unroll
+            for (int m = 0; m < MF; ++m)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
         if (!rows_live) {
         } else if (ncb == CHUNK_CB) {
             // ---- full chunk: k-step s = tap s over channel blocks g = 0..3; fully unrolled (immediate LDS offsets).
@@ -1157,7 +1217,6 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void conv_dma_kernel(TV 
                 have_pend = true;
             }
             ++item_i;
-            if (q + 1 < total_q) cur = decode(first + item_i * stride);
         }
         DTRACE();   // tile epilogue (waves 0..3) done
     }
@@ -1645,27 +1704,36 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
         // the slots hold: those dW rows / columns and db entries are never reduced.  (mmif_debug_set_ragged(0) stages them as before)
         const int px_end = ragged_skip ? (min(8, tx.cb - icg * 8) * WG_XPL + 63) / 64 : WD_XPIECES;
         const int pg_end = WD_XPIECES + (ragged_skip ? (min(8, tg.cb - ocg * 8) * WG_GPL + 63) / 64 : WD_GPIECES);
+        // Piece P = lw + 4 i is an activation piece for i < 10 (and i == 10 on wave 0: piece 40), a gradient piece otherwise, and is
+        // requested iff 4 i < xlim / 4 i < glim: compile-time kinds and limits against constants -- as a piece-indexed loop with P's
+        // kind and range tested per piece, those tests were scalars held across the tile loop (84 spilled, 4-5 v_readlane per piece)
+        static_assert(WD_XPIECES == 10 * D_LOAD + 1 && WD_PIECES <= WDL_ITERS * D_LOAD, "piece split of wgrad_dma_kernel's loader");
+        const int xlim = px_end - lw, glim = pg_end - lw;
+        int nx_in = 0, nx_y0 = 0, nx_x0 = 0;   // image and origin of the tile requested last: emit_signs() of the next iteration reuses them
         auto issue = [&](int tile, int buf) {
-            const int in_ = tile / tpi, tt = tile - in_ * tpi;
-            const int y0 = (tt / tiles_x) * MT, x0 = (tt % tiles_x) * MT;
+            const unsigned in_ = (unsigned)tile / (unsigned)tpi, tt = (unsigned)tile - in_ * (unsigned)tpi;   // (all non-negative)
+            const unsigned ty = tt / (unsigned)tiles_x;
+            const int y0 = (int)ty * MT, x0 = (int)(tt - ty * (unsigned)tiles_x) * MT;
+            nx_in = (int)in_; nx_y0 = y0; nx_x0 = x0;
             const char* src_x = tx.base + ((long long)in_ * tx.img + (long long)(tx.cb_off + icg * 8) * tx.plane) * 16;
             const char* src_g = tg.base + ((long long)in_ * tg.img + (long long)(tg.cb_off + ocg * 8) * tg.plane) * 16;
-            char* dst = s_buf + buf * WD_BUF_BYTES;
+            char* dst = s_buf + buf * WD_BUF_BYTES + lw * 1024;
 #pragma unroll
             for (int i = 0; i < WDL_ITERS; ++i) {
-                const int P = lw + D_LOAD * i;   // wave uniform
                 const int py = (int)((geo[i] >> 8) & 255u), px = (int)(geo[i] & 255u);
-                if (P >= px_end && (P < WD_XPIECES || P >= pg_end)) continue;
-                if (P < WD_XPIECES) {
+                const bool is_x = i < WD_XPIECES / D_LOAD || (i == WD_XPIECES / D_LOAD && lw == 0);   // wave uniform
+                if (is_x) {
+                    if (D_LOAD * i >= xlim) continue;
                     const int y = min(max(reflect_idx(y0 + py - 1, tx.h), 0), tx.h - 1);
                     const int x = min(max(reflect_idx(x0 + px - 1, tx.w), 0), tx.w - 1);
                     const unsigned off = (__umul24((unsigned)y, (unsigned)tx.ws) + (unsigned)x) * 16u + pl_off[i];
-                    __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_x + off), MMIF_LPTR(dst + P * 1024), 16, 0, 0);
-                } else if (P < WD_PIECES) {
+                    __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_x + off), MMIF_LPTR(dst + i * (D_LOAD * 1024)), 16, 0, 0);
+                } else {
+                    if (D_LOAD * i >= glim) continue;   // (glim <= WD_PIECES - lw: also the pieces past the tile's 74)
                     // pixels of a ragged tile that lie outside the image read the zeroed halo ring (stored row h+1 / col w+1)
                     const int y = min(y0 + py, tg.h) + 1, x = min(x0 + px, tg.w) + 1;
                     const unsigned off = (__umul24((unsigned)y, (unsigned)tg.ws) + (unsigned)x) * 16u + pl_off[i];
-                    __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_g + off), MMIF_LPTR(dst + P * 1024), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(MMIF_GPTR(src_g + off), MMIF_LPTR(dst + i * (D_LOAD * 1024)), 16, 0, 0);
                 }
             }
         };
@@ -1674,9 +1742,11 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
         // (t & 31) >> 1, columns 8 (t & 1) .. + 7) -- 8 LDS granules in, ONE 8-byte store out.  The LDS reads are asm: the compiler
         // orders a C++ read of this buffer after ALL outstanding LDS-DMA (vmcnt(0)), i.e. after the NEXT tile's staging has landed.
         typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-        auto emit_signs = [&](int tile, int buf) {
-            const int in_ = tile / tpi, tt = tile - in_ * tpi;
-            const int y0 = (tt / tiles_x) * MT, x0 = (tt % tiles_x) * MT;
+        // this thread's part of its sign-byte address, tile independent (a lane register pair: the loaders have them to spare, the map's
+        // base as a scalar pair did not survive the tile loop)
+        unsigned char* const sgn_lane = sgn.p + ((long long)(icg * 8 + ((lw * 64 + lane) >> 5)) * sgn.hs + (((lw * 64 + lane) & 31) >> 1) + 1) * sgn.pitch +
+                                        8 * (lane & 1) + 1 + SIGN_XOFF;
+        auto emit_signs = [&](int in_, int y0, int x0, int buf) {
             const int t = lw * 64 + lane, pl = t >> 5, py = (t & 31) >> 1, px0 = 8 * (t & 1);
             if (y0 + py >= tx.h || icg * 8 + pl >= tx.cb) return;
             const unsigned lds0 = (unsigned)(size_t)(s_buf + buf * WD_BUF_BYTES) + (unsigned)((pl * WG_XPL + (py + 1) * TP + px0 + 1) * 16);
@@ -1697,7 +1767,8 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
                 }
                 out[i >> 2] |= ((r | (r >> 15)) & 0xffu) << (8 * (i & 3));
             }
-            unsigned char* dst = sgn.p + (((long long)in_ * sgn.cb + icg * 8 + pl) * sgn.hs + y0 + py + 1) * sgn.pitch + x0 + px0 + 1 + SIGN_XOFF;
+            // (= sgn.p + (((long long)in_ * sgn.cb + icg * 8 + pl) * sgn.hs + y0 + py + 1) * sgn.pitch + x0 + px0 + 1 + SIGN_XOFF)
+            unsigned char* dst = sgn_lane + ((long long)in_ * sgn.cb * sgn.hs + y0) * sgn.pitch + x0;
             *reinterpret_cast<uint2*>(dst) = make_uint2(out[0], out[1]);   // (columns past a ragged image edge land in the row's padding)
         };
         const bool signs = sgn.p != nullptr && ocg == 0;
@@ -1705,14 +1776,14 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
         for (int k = 0; k < ntile; ++k) {
             __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's pieces of tile k have landed
             __builtin_amdgcn_s_barrier();
+            const int k_in = nx_in, k_y0 = nx_y0, k_x0 = nx_x0;   // tile k's
             if (k + 1 < ntile) issue(tw.first + (k + 1) * tw.stride, (k & 1) ^ 1);
-            if (signs) emit_signs(tw.first + k * tw.stride, k & 1);
+            if (signs) emit_signs(k_in, k_y0, k_x0, k & 1);
         }
         return;
     }
 
     // ---------------- consumer waves ----------------
-    const int sl = lane & 15, g = lane >> 4;
     const int icf = wave & 3, mp = wave >> 2;   // input-channel fragment (16 ch), output-channel half (2 fragments of 16)
     f32x4 acc[2][9], accb[2];
 #pragma unroll
@@ -1723,6 +1794,16 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
     }
     const uint4 ones_u = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
     const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_u);
+    // The bias sums are the waves' with icf == 0: a scalar, and the tile loop specialised on it -- two copies of the loop, chosen once,
+    // each k-step one basic block (tested per k-step it cut the unrolled tile into 17 blocks).
+    const bool bias_role = __builtin_amdgcn_readfirstlane(icf == 0) != 0;
+    auto tile_loop = [&](auto bias_c) {
+    constexpr bool BIAS = decltype(bias_c)::value != 0;
+    // (lane coordinates derived inside each copy, behind an asm the compiler cannot hoist: shared by the two copies they stayed live
+    // across the first copy's loop for the second, and were spilled there)
+    int lane_t;
+    __asm__ volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_t));
+    const int sl = lane_t & 15, g = lane_t >> 4;
     // per-lane transpose-read addressing (see wgrad_mfma_kernel): in-group lane sl supplies pixel row (sl>>2), chunk (sl&3)
     const int tr_row = sl >> 2, tr_c = sl & 3;
     const int lane_plane = tr_c >> 1, lane_byte = (tr_c & 1) * 8;
@@ -1748,6 +1829,8 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
             const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, base + 4 * 16));
             return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
         };
+        // (A ring of FOUR rows -- row s2 + 3 requested a k-step ahead of its use -- fits the 168 registers exactly and was measured:
+        // 354.2 -> 353.4 us per launch, the step 3.572 -> 3.573 ms.  Not kept.)
         bf16x8 xr[3][3], a[2][2];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -1763,7 +1846,7 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
 #pragma unroll
                 for (int m = 0; m < 2; ++m) a[(s2 + 1) & 1][m] = ld_g(s2 + 1, m);
             }
-            if (icf == 0) {
+            if (BIAS) {
 #pragma unroll
                 for (int m = 0; m < 2; ++m) accb[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s2 & 1][m], ones, accb[m], 0, 0, 0);
             }
@@ -1774,18 +1857,27 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
                 for (int m = 0; m < 2; ++m)
                     acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s2 & 1][m], xr[(s2 + u) % 3][v], acc[m][t], 0, 0, 0);
             }
+            // (Pinning the ten reads one by one onto the first MFMAs with sched_group_barrier, as conv_dma_kernel does, was built and
+            // dropped: the pinned order needs 45 more vector registers than the 168 there are.)
         }
     }
+    };
+    if (bias_role) tile_loop(IC<1>());
+    else tile_loop(IC<0>());
+    // (lane coordinates re-derived behind an asm the compiler cannot hoist: kept live across the tile loop for this epilogue they were
+    // the kernel's four spilled vector registers)
+    int lane_e;
+    __asm__ volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
     // lane (g, sl) reg r of fragment m holds (oc = 16*(2*mp + m) + 4g + r, ic = 16*icf + sl) for tap t; bias sums: column sl == 0
     float* dst = partial + ((long long)gi * npairs + pair) * WD_PER;
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int oc = 16 * (2 * mp + m) + 4 * g + r, ic = 16 * icf + sl;
+            const int oc = 16 * (2 * mp + m) + 4 * (lane_e >> 4) + r, ic = 16 * icf + (lane_e & 15);
 #pragma unroll
             for (int t = 0; t < 9; ++t) dst[(oc * 64 + ic) * 9 + t] = acc[m][t][r];
-            if (icf == 0 && sl == 0) dst[64 * 64 * 9 + oc] = accb[m][r];
+            if (bias_role && (lane_e & 15) == 0) dst[64 * 64 * 9 + oc] = accb[m][r];
         }
 }
 
@@ -2039,9 +2131,12 @@ __global__ __launch_bounds__(512, NXB == 4 ? 1 : 2) void bwd_pair_kernel(TV tx, 
 // vmcnt before any LDS access of that wave.)  The bias sums moved into the tap-row-1 wave, which already holds the transposed gradient
 // fragments (same MFMA(a, ones) sequence => bit-identical); dgrad / wgrad k-loops, fold steps and epilogue are bwd_pair_kernel's.
 // LDS: 2 x 61 KiB + 36 KiB image = 158 KiB (<4, 2>: one block per CU), 2 x 31 KiB + 10 KiB (<2, 1>: two blocks per CU).
-template <int NXB, int NGB>
+// (DIAG: the instantiation that carries the $MMIF_ABLATE bp= timing ablations, as in conv_dma_kernel; its trace pointer is unused)
+template <int NXB, int NGB, bool DIAG = false>
 __global__ __launch_bounds__(512, NXB == 4 ? 1 : 2) void bwd_pair_dma_kernel(TV tx, TV tg, TV tgx, const uint4* __restrict__ wpk, float* __restrict__ partial,
-                                                                             int tiles_x, int tpi, int total, int G, int abl) {
+                                                                             int tiles_x, int tpi, int total, int G, DiagArgs<DIAG> diag) {
+    int abl = 0;   // a constant in the shipped form: the tests below fold away
+    if constexpr (DIAG) abl = diag.abl;
     constexpr int MF = NXB, TP = MT + 2;
     constexpr int CIN = 16 * NXB, COUT = 16 * NGB;
     constexpr int NCB = 2 * NGB;
@@ -2297,12 +2392,19 @@ int bwd_pair(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, f
     static int bp_abl = -1;   // $MMIF_ABLATE bp= (timing ablations, wrong results): 1 no tile requests after the first, 2 no gx stores, 4 no wgrad loops, 8 no dgrad k-loops
     if (bp_abl < 0) bp_abl = ablate_env("bp");   // (the loader reads the gradient's zero ring for rows / columns past the image)
     const bool use_dma = r.kernel == PairRoute::DMA;
-    if (cin == 64 && use_dma)
-        hipLaunchKernelGGL((bwd_pair_dma_kernel<4, 2>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, bp_abl);
+    DiagArgs<true> dg;
+    dg.trace = nullptr;
+    dg.abl = bp_abl;
+    if (cin == 64 && use_dma && bp_abl != 0)
+        hipLaunchKernelGGL((bwd_pair_dma_kernel<4, 2, true>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, dg);
+    else if (cin == 64 && use_dma)
+        hipLaunchKernelGGL((bwd_pair_dma_kernel<4, 2>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, DiagArgs<false>{});
     else if (cin == 64)
         hipLaunchKernelGGL((bwd_pair_kernel<4, 2>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G);
+    else if (use_dma && bp_abl != 0)
+        hipLaunchKernelGGL((bwd_pair_dma_kernel<2, 1, true>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, dg);
     else if (use_dma)
-        hipLaunchKernelGGL((bwd_pair_dma_kernel<2, 1>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, bp_abl);
+        hipLaunchKernelGGL((bwd_pair_dma_kernel<2, 1>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G, DiagArgs<false>{});
     else
         hipLaunchKernelGGL((bwd_pair_kernel<2, 1>), dim3(r.G), dim3(512), 0, st, tx, tg, tgx, (const uint4*)wpk_dgrad, ws, r.tiles_x, r.tpi, r.total, r.G);
     if (int rc = check_launch("bwd_pair")) return rc;
@@ -2336,15 +2438,31 @@ static int launch_conv_dma(const ConvRoute& r, bool dgrad, const TV& tin, const 
     else { dupv.out = tout; dupv.mask = tout; dupv.frag = -1; }
     const int nmb = n_mblocks(n_out);
     const int m16p = nmb * 4 * 16;
-#define DMA_GO(D_, L_, DUP_)                                                                                                                          \
-    hipLaunchKernelGGL((conv_dma_kernel<D_, L_, DUP_>), dim3(r.G), dim3((D_CONS + D_LOAD) * 64), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, n_out, \
-                       m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, nmb, g_trace, conv_abl(), r.org, sgn, dupv)
-    if (!dgrad) DMA_GO(false, 0, false);
-    else if (r.dup) DMA_GO(true, 0, true);
-    else if (r.lmask == 2) DMA_GO(true, 2, false);
-    else if (r.lmask == 1) DMA_GO(true, 1, false);
-    else DMA_GO(true, 0, false);
+    // the diagnostic instantiation only when a diagnostic is asked for (a trace buffer, $MMIF_ABLATE conv=); it exists for the forms the
+    // tools reach -- the DenseFuse dgrad with masked copies has none
+    const bool diag = g_trace != nullptr || conv_abl() != 0;
+    if (diag && dgrad && r.dup) {
+        set_error("conv_dma dgrad: the masked-copies form has no diagnostic instantiation (unset the trace buffer / $MMIF_ABLATE conv=)");
+        return MMIF_EINVAL;
+    }
+    DiagArgs<true> dg;
+    dg.trace = g_trace;
+    dg.abl = conv_abl();
+#define DMA_GO_(D_, L_, DUP_, DIAG_, DG_)                                                                                                             \
+    hipLaunchKernelGGL((conv_dma_kernel<D_, L_, DUP_, DIAG_>), dim3(r.G), dim3((D_CONS + D_LOAD) * 64), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, \
+                       n_out, m16p, relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, r.tiles_x, r.tiles_y, nmb, r.org, sgn, dupv, DG_)
+#define DMA_GO(D_, L_)                                  \
+    do {                                                \
+        if (diag) DMA_GO_(D_, L_, false, true, dg);     \
+        else DMA_GO_(D_, L_, false, false, DiagArgs<false>{}); \
+    } while (0)
+    if (!dgrad) DMA_GO(false, 0);
+    else if (r.dup) DMA_GO_(true, 0, true, false, DiagArgs<false>{});
+    else if (r.lmask == 2) DMA_GO(true, 2);
+    else if (r.lmask == 1) DMA_GO(true, 1);
+    else DMA_GO(true, 0);
 #undef DMA_GO
+#undef DMA_GO_
     return check_launch(dgrad ? "conv_dma dgrad" : "conv_dma fwd");
 }
 

@@ -8,8 +8,8 @@ out=$OUT/${tag}_ubench_bwd_pair_ablation.txt
 echo "# avg us per launch inside bench.py (B=32 256x256 bf16, rocprofv3 kernel trace, 13 launches): decode.2 (64->32) | decode.3 (32->16)" > $out
 row() {
   tools/prof_bench.sh bp_$1 --no-parity-path > /dev/null 2>&1
-  a=$(grep "bwd_pair_$3kernel<4, 2>" $OUT/kstats_bp_$1.txt | awk '{print $(NF-3)}')
-  b=$(grep "bwd_pair_$3kernel<2, 1>" $OUT/kstats_bp_$1.txt | awk '{print $(NF-3)}')
+  a=$(grep "bwd_pair_$3kernel<4, 2[,>]" $OUT/kstats_bp_$1.txt | awk '{print $(NF-3)}')
+  b=$(grep "bwd_pair_$3kernel<2, 1[,>]" $OUT/kstats_bp_$1.txt | awk '{print $(NF-3)}')
   printf "%-78s %8s %8s\n" "$2" "$a" "$b" >> $out
 }
 MMIF_ABLATE=bp=0 row 0 "DMA-staged kernel (loader wave, double-buffered tile, one barrier per tile)" "dma_"
