@@ -385,7 +385,8 @@ int mmif_pairconv_fwd(const mmif_tensor* a, const mmif_tensor* b, const float* w
                       const mmif_tensor* res2, void* stream);
 /* gxa/gxb (halo-1 views): padded-domain gradient w.r.t. a, b from ga (and gb when nout = 2; already masked by the layer's
  * own ReLU); `add` (optional, halo 0/1): gradient of a residual path, added to both; mask_bits: channel blocks multiplied
- * by [xa > 0] / [xb > 0].  The caller folds the halo afterwards (mmif_fold_halo). */
+ * by [xa > 0] / [xb > 0].  The caller folds the halo afterwards (mmif_fold_halo).  An unfolded halo-1 `add` is folded while
+ * loading.  All four pair-conv calls need h, w >= 2 (reflect padding by 1). */
 int mmif_pairconv_dgrad(const mmif_tensor* ga, const mmif_tensor* gb, const float* w, int32_t nout, const mmif_tensor* xa,
                         const mmif_tensor* xb, const mmif_tensor* gxa, const mmif_tensor* gxb, uint64_t mask_bits,
                         const mmif_tensor* add, void* stream);

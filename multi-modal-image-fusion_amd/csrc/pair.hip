@@ -865,6 +865,9 @@ extern "C" int mmif_pairconv_dgrad(const mmif_tensor* ga, const mmif_tensor* gb,
     MMIF_REQUIRE(nout == 1 || nout == 2, "pairconv_dgrad: nout must be 1 or 2 (got %d)", nout);
     MMIF_REQUIRE(w != nullptr, "pairconv_dgrad: w is NULL");
     MMIF_REQUIRE(same_shape(ga, gxa) && same_shape(ga, gxb) && gxa->halo == 1 && gxb->halo == 1, "pairconv_dgrad: gx must be halo-1 views of g's shape");
+    // the layer this is the backward of does not exist below 2 x 2 (mmif_pairconv_fwd refuses): the ring's ReLU mask and the fold of an
+    // unfolded `add` both take the reflect source of a ring pixel
+    MMIF_REQUIRE(ga->h >= 2 && ga->w >= 2, "pairconv_dgrad: reflect padding needs h, w >= 2");
     MMIF_REQUIRE(ga->halo == 0 || (ga->flags & MMIF_T_FOLDED), "pairconv_dgrad: a halo-1 gradient must be folded first (mmif_fold_halo)");
     if (nout == 2 && gb) MMIF_REQUIRE(gb->halo == 0 || (gb->flags & MMIF_T_FOLDED), "pairconv_dgrad: a halo-1 gradient must be folded first (mmif_fold_halo)");
     if (nout == 2) {
@@ -903,6 +906,7 @@ extern "C" int mmif_pairconv_wgrad(const mmif_tensor* xa, const mmif_tensor* xb,
     MMIF_REQUIRE(nout == 1 || nout == 2, "pairconv_wgrad: nout must be 1 or 2 (got %d)", nout);
     MMIF_REQUIRE(dw != nullptr && db != nullptr, "pairconv_wgrad: dw/db is NULL");
     MMIF_REQUIRE(same_shape(xa, xb) && same_shape(xa, ga) && xa->halo == 0 && xb->halo == 0, "pairconv_wgrad: shape mismatch");
+    MMIF_REQUIRE(xa->h >= 2 && xa->w >= 2, "pairconv_wgrad: reflect padding needs h, w >= 2");
     if (nout == 2) {
         MMIF_REQUIRE(gb != nullptr, "pairconv_wgrad: gb is NULL with nout = 2");
         if (int rc = validate_tensor(gb, "gb")) return rc;

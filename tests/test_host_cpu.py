@@ -62,6 +62,41 @@ def test_c_abi_validation_of_the_widened_entry_points_without_gpu():
     assert lib.mmif_pairconv_wgrad_workspace() > 0
     assert lib.mmif_pairconv_bwd(r(ok), None, w, 1, r(ok), r(ok), r(h1), r(h1), 0, None, w, w, 0, None, 0, None) == -3   # workspace
     assert lib.mmif_pairconv_bwd(r(ok), None, w, 2, r(ok), r(ok), r(h1), r(h1), 0, None, w, w, 0, None, 0, None) == -1   # gb missing
+    # ---- the pair-conv family's edge shapes and gradient states (tests/pair_cases.py defines everything these calls accept)
+    big = (ctypes.c_char * (1 << 20))()
+    ws, nws = ctypes.addressof(big), 1 << 20
+
+    def t(h, wd, halo=0, flags=0, cb=1, dtype=1):
+        return MmifTensor(base, dtype, 1, h, wd, halo, cb, 0, cb, flags)
+    for h, wd in ((1, 4), (4, 1), (1, 1)):      # reflect padding by 1 has no source below 2 x 2: all four refuse, with and without a mask
+        x, g, gx = t(h, wd), t(h, wd), t(h, wd, 1)
+        calls = [lambda: lib.mmif_pairconv_fwd(r(x), r(x), w, None, 1, r(x), None, 1, None, None, None),
+                 lambda: lib.mmif_pairconv_dgrad(r(g), None, w, 1, r(x), r(x), r(gx), r(gx), 1, None, None),
+                 lambda: lib.mmif_pairconv_dgrad(r(g), None, w, 1, None, None, r(gx), r(gx), 0, None, None),
+                 lambda: lib.mmif_pairconv_wgrad(r(x), r(x), r(g), None, 1, w, w, 0, ws, nws, None),
+                 lambda: lib.mmif_pairconv_bwd(r(g), None, w, 1, r(x), r(x), r(gx), r(gx), 0, None, w, w, 0, ws, nws, None)]
+        for call in calls:
+            assert call() == -1
+            assert b"reflect padding needs h, w >= 2" in lib.mmif_last_error()
+    g4, gx4, f4 = t(4, 4), t(4, 4, 1), t(4, 4, 1, 1)
+    # `add`: shape and dtype must be g's in both calls; an unfolded halo-1 add is mmif_pairconv_dgrad's to fold, mmif_pairconv_bwd refuses it
+    for bad in (t(4, 5), t(5, 4), t(4, 4, cb=2), t(4, 4, dtype=0), t(4, 5, 1), t(4, 4, 1, 1, dtype=0)):
+        assert lib.mmif_pairconv_dgrad(r(g4), None, w, 1, None, None, r(gx4), r(gx4), 0, r(bad), None) == -1
+        assert b"pairconv_dgrad: add shape mismatch" in lib.mmif_last_error()
+        assert lib.mmif_pairconv_bwd(r(g4), None, w, 1, r(g4), r(g4), r(gx4), r(gx4), 0, r(bad), w, w, 0, ws, nws, None) == -1
+        assert b"pairconv_bwd: add shape mismatch" in lib.mmif_last_error()
+    assert lib.mmif_pairconv_bwd(r(g4), None, w, 1, r(g4), r(g4), r(gx4), r(gx4), 0, r(gx4), w, w, 0, ws, nws, None) == -1
+    assert b"pairconv_bwd: a halo-1 residual gradient must be folded first" in lib.mmif_last_error()
+    assert lib.mmif_pairconv_bwd(r(gx4), None, w, 1, r(g4), r(g4), r(gx4), r(gx4), 0, None, w, w, 0, ws, nws, None) == -1
+    assert b"pairconv_bwd: a halo-1 gradient must be folded first" in lib.mmif_last_error()
+    assert lib.mmif_pairconv_bwd(r(g4), r(f4), w, 2, r(g4), r(g4), r(gx4), r(gx4), 0, None, w, w, 0, ws, nws, None) == -1
+    assert b"ga and gb must have the same halo" in lib.mmif_last_error()
+    # activations are halo 0 everywhere; gx is halo 1
+    assert lib.mmif_pairconv_wgrad(r(f4), r(f4), r(g4), None, 1, w, w, 0, ws, nws, None) == -1
+    assert lib.mmif_pairconv_dgrad(r(g4), None, w, 1, r(f4), r(f4), r(gx4), r(gx4), 1, None, None) == -1
+    assert b"xa/xb shape mismatch" in lib.mmif_last_error()
+    assert lib.mmif_pairconv_dgrad(r(g4), None, w, 1, None, None, r(g4), r(g4), 0, None, None) == -1
+    assert b"gx must be halo-1 views" in lib.mmif_last_error()
     f = (ctypes.c_float * 16)()
     assert lib.mmif_ssim_loss_mode(f, f, f, 1, 32, 32, 1.0, 1.0, 7, f, None, f, 1 << 20, None) == -1
     assert b"only supported ['ssim', 'w-ssim', 'ms-ssim', 'msw-ssim'] mode" in lib.mmif_last_error()
