@@ -404,7 +404,8 @@ int mmif_pairconv_bwd(const mmif_tensor* ga, const mmif_tensor* gb, const float*
                       size_t workspace_bytes, void* stream);
 
 /* ---- NestFuse glue: nn.MaxPool2d(2,2) (core/model.py:332-335), nn.Upsample(x2,'nearest') + ReflectionPad2d to the
- *      skip's shape (core/block.py:965-991), threshold_backward of a ReLU output ---- */
+ *      skip's shape (core/block.py:965-991; forward and both backwards accept 2h <= H < 4h and 2w <= W < 4w: one reflection),
+ *      threshold_backward of a ReLU output ---- */
 int mmif_maxpool2x2_fwd(const mmif_tensor* x, const mmif_tensor* y, void* stream);
 int mmif_maxpool2x2_bwd(const mmif_tensor* x, const mmif_tensor* g, const mmif_tensor* gx, int32_t accumulate, void* stream);
 int mmif_upsample2x_fwd(const mmif_tensor* x, const mmif_tensor* y, void* stream);

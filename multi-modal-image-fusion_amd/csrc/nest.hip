@@ -388,7 +388,8 @@ extern "C" int mmif_upsample2x_fwd(const mmif_tensor* x, const mmif_tensor* y, v
 static int upsample2x_bwd_impl(const mmif_tensor* g, const mmif_tensor* gx, int32_t accumulate, const mmif_tensor* xmask, void* stream) {
     if (int rc = validate_tensor(g, "g")) return rc;
     if (int rc = validate_tensor(gx, "gx")) return rc;
-    MMIF_REQUIRE(same_nc(g, gx) && g->h >= 2 * gx->h && g->w >= 2 * gx->w, "upsample2x_bwd: shape mismatch");
+    MMIF_REQUIRE(same_nc(g, gx) && g->h >= 2 * gx->h && g->w >= 2 * gx->w && g->h - 2 * gx->h < 2 * gx->h && g->w - 2 * gx->w < 2 * gx->w,
+                 "upsample2x_bwd: shape mismatch (g must be >= 2x gx and less than 4x: one reflection)");
     if (xmask != nullptr) {
         if (int rc = validate_tensor(xmask, "x")) return rc;
         MMIF_REQUIRE(same_nc(xmask, gx) && xmask->halo == 0 && xmask->h == gx->h && xmask->w == gx->w, "upsample2x_bwd_relu: x does not match gx");

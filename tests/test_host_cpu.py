@@ -129,6 +129,100 @@ def test_c_abi_validation_of_the_widened_entry_points_without_gpu():
     assert b"ksize must be 1 or 3" in lib.mmif_last_error()
 
 
+def test_c_abi_validation_of_the_blocked_glue_entry_points_without_gpu():
+    """csrc/nest.hip and the element-fusion / layout kernels of csrc/misc.hip (tests/nest_cases.py defines everything these calls accept): every
+    shape, halo, dtype, mode and workspace refusal comes before any launch"""
+    from mmif._lib import MmifTensor, lib
+    buf = (ctypes.c_char * 4096)()
+    base = ctypes.addressof(buf)
+    r = ctypes.byref
+    err = lib.mmif_last_error
+
+    def t(h, wd, halo=0, flags=0, cb=1, dtype=1, n=1):
+        return MmifTensor(base, dtype, n, h, wd, halo, cb, 0, cb, flags)
+    # ---- nearest x2 + reflect pad: the target is at least 2x the source and less than 4x (one reflection), forward and both backwards
+    x2 = t(2, 2)
+    for H, W in ((8, 4), (4, 8), (9, 5), (8, 8), (3, 4), (4, 3)):
+        assert lib.mmif_upsample2x_fwd(r(x2), r(t(H, W)), None) == -1
+        assert b"upsample2x_fwd: target shape" in err()
+        for g in (t(H, W), t(H, W, 1), t(H, W, 1, 1)):
+            assert lib.mmif_upsample2x_bwd(r(g), r(t(2, 2, 1)), 0, None) == -1
+            assert b"upsample2x_bwd: shape mismatch" in err()
+            assert lib.mmif_upsample2x_bwd_relu(r(g), r(t(2, 2, 1)), 1, r(x2), None) == -1
+            assert b"upsample2x_bwd: shape mismatch" in err()
+    assert lib.mmif_upsample2x_fwd(r(t(2, 2, 1)), r(t(4, 4)), None) == -1 and lib.mmif_upsample2x_fwd(r(x2), r(t(4, 4, 1)), None) == -1      # halo
+    assert lib.mmif_upsample2x_fwd(r(x2), r(t(4, 4, cb=2)), None) == -1 and lib.mmif_upsample2x_fwd(r(x2), r(t(4, 4, dtype=0)), None) == -1
+    assert lib.mmif_upsample2x_bwd(r(t(4, 4, n=2)), r(t(2, 2, 1)), 0, None) == -1 and lib.mmif_upsample2x_bwd(r(t(4, 4, dtype=0)), r(t(2, 2, 1)), 0, None) == -1
+    assert lib.mmif_upsample2x_bwd_relu(r(t(4, 4)), r(t(2, 2, 1)), 0, None, None) == -1
+    assert b"upsample2x_bwd_relu: x is NULL" in err()
+    for bad in (t(2, 3), t(2, 2, 1), t(2, 2, cb=2), t(2, 2, dtype=0)):
+        assert lib.mmif_upsample2x_bwd_relu(r(t(4, 4)), r(t(2, 2, 1)), 0, r(bad), None) == -1
+        assert b"upsample2x_bwd_relu: x does not match gx" in err()
+    # ---- 2x2 max-pool
+    x5 = t(5, 4)
+    for y in (t(3, 2), t(2, 3), t(2, 2, 1), t(2, 2, cb=2), t(2, 2, dtype=0)):
+        assert lib.mmif_maxpool2x2_fwd(r(x5), r(y), None) == -1
+        assert b"maxpool2x2_fwd: shape mismatch" in err()
+    assert lib.mmif_maxpool2x2_fwd(r(t(5, 4, 1)), r(t(2, 2)), None) == -1
+    assert lib.mmif_maxpool2x2_fwd(r(t(1, 4)), r(t(1, 2)), None) == -1          # a one-row image has no 2x2 window
+    for fn in (lib.mmif_maxpool2x2_bwd, lib.mmif_maxpool2x2_bwd_relu):
+        for x, g, gx in ((x5, t(3, 2), t(5, 4, 1)), (x5, t(2, 2), t(4, 4, 1)), (x5, t(2, 2), t(5, 5, 1)), (t(5, 4, 1), t(2, 2), t(5, 4, 1)),
+                         (x5, t(2, 2, dtype=0), t(5, 4, 1)), (x5, t(2, 2), t(5, 4, 1, cb=2))):
+            assert fn(r(x), r(g), r(gx), 0, None) == -1
+            assert b"maxpool2x2_bwd: shape mismatch" in err()
+        assert fn(r(x5), None, r(t(5, 4, 1)), 0, None) == -1
+        assert b"null tensor" in err()
+    # ---- in-place ReLU mask
+    for x, g in ((t(4, 4), t(4, 5, 1)), (t(4, 4, 1), t(4, 4, 1)), (t(4, 4), t(4, 4, 1, cb=2)), (t(4, 4, dtype=0), t(4, 4))):
+        assert lib.mmif_relu_mask(r(x), r(g), None) == -1
+        assert b"relu_mask: shape mismatch" in err()
+    # ---- attention fusion: mode, shapes, activations at halo 0, workspace
+    a, g1 = t(4, 4), t(4, 4, 1)
+    big = (ctypes.c_char * (1 << 16))()
+    ws, nws = ctypes.addressof(big), 1 << 16
+    assert lib.mmif_fuse_attn_workspace(1, 8) <= nws
+    assert lib.mmif_fuse_attn_fwd(r(a), r(a), r(a), 3, ws, nws, None) == -1
+    assert b"only supported ['sa', 'ca', 'sca', 'wavg'] mode" in err()
+    for x, y, o in ((a, t(4, 5), a), (a, a, t(5, 4)), (g1, a, a), (a, a, g1), (a, t(4, 4, cb=2), a), (a, a, t(4, 4, dtype=0))):
+        assert lib.mmif_fuse_attn_fwd(r(x), r(y), r(o), 2, ws, nws, None) == -1
+        assert b"fuse_attn_fwd: shape mismatch" in err()
+    assert lib.mmif_fuse_attn_fwd(r(a), r(a), r(a), 2, ws, 16, None) == -3
+    for fn in (lib.mmif_fuse_attn_bwd, lib.mmif_fuse_attn_bwd_cached):
+        assert fn(r(a), r(a), r(g1), r(g1), r(g1), -1, 0, ws, nws, None) == -1
+        assert b"only supported ['sa', 'ca', 'sca', 'wavg'] mode" in err()
+        for x, y, g, ga, gb in ((g1, a, g1, g1, g1), (a, g1, g1, g1, g1), (a, a, t(4, 5, 1), g1, g1), (a, a, g1, t(5, 4, 1), g1), (a, a, g1, g1, t(4, 5, 1)),
+                                (a, a, g1, t(4, 4, 1, cb=2), g1), (a, a, t(4, 4, 1, dtype=0), g1, g1)):
+            assert fn(r(x), r(y), r(g), r(ga), r(gb), 0, 0, ws, nws, None) == -1
+            assert b"fuse_attn_bwd: shape mismatch" in err()
+        assert fn(r(a), r(a), r(g1), r(g1), r(g1), 1, 0, ws, 16, None) == -3
+        assert fn(r(a), r(a), r(g1), None, r(g1), 1, 0, ws, nws, None) == -1
+    # ---- element fusion: a / b are only looked at when the mode or the mask needs them
+    assert lib.mmif_fuse_elem_fwd(r(a), r(a), r(a), 3, None) == -1
+    assert b"only supported ['sum', 'mean', 'max'] mode" in err()
+    for x, y, o in ((a, g1, a), (g1, g1, g1), (a, a, g1), (a, t(4, 5), a), (a, a, t(4, 4, dtype=0))):
+        assert lib.mmif_fuse_elem_fwd(r(x), r(y), r(o), 0, None) == -1
+        assert b"fuse_elem_fwd: shape/halo mismatch" in err()
+    assert lib.mmif_fuse_elem_bwd(None, None, r(g1), r(g1), r(g1), -1, 0, None) == -1
+    assert b"only supported ['sum', 'mean', 'max'] mode" in err()
+    for g, ga, gb in ((g1, a, g1), (g1, g1, a), (a, g1, g1), (g1, t(4, 5, 1), g1), (g1, g1, t(4, 4, 1, cb=2))):
+        assert lib.mmif_fuse_elem_bwd(None, None, r(g), r(ga), r(gb), 0, 0, None) == -1
+        assert b"fuse_elem_bwd: gradient shape/halo mismatch" in err()
+    for mode, mask in ((2, 0), (0, 1), (1, 1)):
+        assert lib.mmif_fuse_elem_bwd(None, r(a), r(g1), r(g1), r(g1), mode, mask, None) == -1
+        assert b"null tensor" in err()
+        for x, y in ((g1, a), (a, g1), (t(4, 5), a), (a, t(4, 4, dtype=0))):
+            assert lib.mmif_fuse_elem_bwd(r(x), r(y), r(g1), r(g1), r(g1), mode, mask, None) == -1
+            assert b"fuse_elem_bwd: a/b mismatch" in err()
+    # ---- layout conversions: the logical channel count fits the view
+    f = (ctypes.c_float * 16)()
+    for c in (0, -1, 9):
+        assert lib.mmif_nchw_to_blocked(f, c, r(a), None) == -1
+        assert b"nchw_to_blocked: c=" in err()
+        assert lib.mmif_blocked_to_nchw(r(a), f, c, None) == -1
+        assert b"blocked_to_nchw: c=" in err()
+    assert lib.mmif_nchw_to_blocked(f, 8, None, None) == -1 and lib.mmif_blocked_to_nchw(None, f, 8, None) == -1
+
+
 @pytest.mark.parametrize("name", ["PFNetv1", "PFNetv2", "DenseFuse", "VIFNet", "NestFuse", "RFNNest", "DeepFuse", "DBNet", "SEDRFuse", "IFCNN",
                                   "DIFNet", "PMGI", "UNFusion", "MAFusion", "Res2Fusion"])
 def test_state_dict_manifest_and_init(name):
