@@ -183,7 +183,10 @@ int mmif_bilinear_up_bwd(const float* g, float* dx, int64_t planes, int32_t h, i
  * and the unbiased variance), 1 = nn.BatchNorm2d in eval mode (running buffers), 2 = nn.GroupNorm(c, c) (one group per channel:
  * per-(sample, channel) statistics; SEDRFuse core/model.py:249-260).  act: 0 none, 1 ReLU, 2 LeakyReLU(slope), 3 Tanh, 4 ReLU6.
  * stats receives (mean, rstd) per channel (kinds 0, 1: 2 c floats) or per plane (kind 2: 2 n c floats) for the backward pass.
- * Backward: dx, dgamma, dbeta (either may be NULL) from x, y (the forward's output), gy. */
+ * Backward: dx, dgamma, dbeta (either may be NULL) from x, y (the forward's output), gy.
+ * kind 0 takes running_mean and running_var together or not at all (one without the other is refused); kind 2 ignores them.
+ * A statistic over m = 1 element (n = 1, hw = 1 for kind 0; hw = 1 for kind 2; torch refuses it in training) is defined as var = 0,
+ * y = act(beta), dx = 0, and running_var is updated with the biased value (0), the factor m / (m - 1) being left out. */
 size_t mmif_norm_workspace(int32_t n, int32_t c);
 int mmif_norm_act_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stats, float* running_mean,
                       float* running_var, int32_t n, int32_t c, int64_t hw, int32_t kind, float eps, float momentum, int32_t act,
@@ -610,7 +613,10 @@ int mmif_patch_feed(const uint8_t* bank, int64_t n_patches, int32_t patch, const
 /* ---- optimiser (train.py:72-75,319): clip_grad_norm_(max_norm) + Adam on flat fp32 buffers ---- */
 size_t mmif_clip_adam_workspace(int64_t numel);
 /* grad_scale multiplies the gradients first (1/world after a SUM all-reduce).  max_norm <= 0
- * disables clipping.  norm_out (device float[1], may be NULL) receives the pre-clip global L2 norm. */
+ * disables clipping.  norm_out (device float[1], may be NULL) receives the pre-clip global L2 norm.
+ * params, grads, both moments and the workspace must not be NULL.  Non-finite gradients behave as in torch: a NaN norm gives a NaN
+ * clip coefficient, so every moment and parameter becomes NaN; an infinite norm gives coefficient 0 (the infinite element becomes
+ * NaN, every other gradient counts as 0).  With clipping disabled only the non-finite elements themselves are poisoned. */
 int mmif_clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t numel,
                         float lr, float beta1, float beta2, float eps, int32_t step, float max_norm,
                         float grad_scale, float* norm_out, void* workspace, size_t workspace_bytes, void* stream);

@@ -239,7 +239,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     if (threadIdx.x == 0) {
         const float norm = sqrtf(t) * grad_scale;
         float coef = 1.f;
-        if (max_norm > 0.f) coef = fminf(1.f, max_norm / (norm + 1e-6f));
+        if (max_norm > 0.f) {
+            const float q = max_norm / (norm + 1e-6f);
+            coef = q != q ? q : fminf(1.f, q);   // torch's clamp(max=1) keeps a NaN norm: every gradient, hence every parameter, becomes NaN
+        }
         s_gs = coef * grad_scale;
         if (blockIdx.x == 0) {
             stats[0] = norm;
@@ -382,10 +385,13 @@ extern "C" int mmif_clip_adam_step(float* params, const float* grads, float* exp
                                    float grad_scale, float* norm_out, void* workspace, size_t workspace_bytes,
                                    void* stream) {
     MMIF_REQUIRE(numel > 0 && step >= 1, "clip_adam_step: numel=%lld step=%d", (long long)numel, step);
+    MMIF_REQUIRE(params != nullptr && grads != nullptr && exp_avg != nullptr && exp_avg_sq != nullptr,
+                 "clip_adam_step: params, grads, exp_avg and exp_avg_sq must not be NULL");
     if (workspace_bytes < mmif_clip_adam_workspace(numel)) {
         set_error("clip_adam_step: workspace too small");
         return MMIF_EWORKSPACE;
     }
+    MMIF_REQUIRE(workspace != nullptr, "clip_adam_step: workspace is NULL");
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
     float* stats = partial + ADAM_PARTIALS;

@@ -224,6 +224,7 @@ extern "C" int mmif_norm_act_fwd(const float* x, const float* gamma, const float
     MMIF_REQUIRE(x != nullptr && y != nullptr && stats != nullptr && n > 0 && c > 0 && hw > 0, "norm_act_fwd: bad arguments");
     MMIF_REQUIRE(kind >= 0 && kind <= 2 && act >= 0 && act <= 4, "norm_act_fwd: bad kind / activation");
     MMIF_REQUIRE(kind != 1 || (running_mean != nullptr && running_var != nullptr), "norm_act_fwd: eval mode needs the running statistics");
+    MMIF_REQUIRE(kind != 0 || (running_mean == nullptr) == (running_var == nullptr), "norm_act_fwd: running_mean and running_var come together");
     if (kind != 1 && (workspace == nullptr || workspace_bytes < mmif_norm_workspace(n, c))) {
         set_error("norm_act_fwd: workspace too small");
         return MMIF_EWORKSPACE;

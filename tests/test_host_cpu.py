@@ -223,6 +223,100 @@ def test_c_abi_validation_of_the_blocked_glue_entry_points_without_gpu():
     assert lib.mmif_nchw_to_blocked(f, 8, None, None) == -1 and lib.mmif_blocked_to_nchw(None, f, 8, None) == -1
 
 
+def test_c_abi_validation_of_the_norm_and_optimiser_entry_points_without_gpu():
+    """csrc/norm.hip's nine entry points and mmif_clip_adam_step (tests/norm_cases.py and tests/optim_cases.py define everything these calls
+    accept): every refusal comes before any launch, with its return code and message.  None of these calls may ever reach a device."""
+    from mmif._lib import lib
+    err = lib.mmif_last_error
+    fbuf = (ctypes.c_float * 4096)()
+    f = ctypes.addressof(fbuf)
+    big = (ctypes.c_char * (1 << 16))()
+    ws, nws = ctypes.addressof(big), 1 << 16
+    n, c, hw = 2, 3, 5
+    need = lib.mmif_norm_workspace(n, c)
+    assert need == (n * c + c) * 2 * 8 and lib.mmif_norm_workspace(3, 257) == (3 * 257 + 257) * 16 and lib.mmif_norm_workspace(1, 1) == 32
+    assert lib.mmif_clip_adam_workspace(1) == lib.mmif_clip_adam_workspace(3 * 262144 + 17) == (1024 + 8) * 4
+
+    def refused(call, msg, code=-1):
+        assert call() == code, msg
+        assert msg in err(), (msg, err())
+
+    # ---- mmif_norm_act_fwd(x, gamma, beta, y, stats, running_mean, running_var, n, c, hw, kind, eps, momentum, act, slope, ws, bytes, stream)
+    def fwd(x=f, y=f, stats=f, rm=None, rv=None, n=n, c=c, hw=hw, kind=0, act=1, ws=ws, nws=nws):
+        return lambda: lib.mmif_norm_act_fwd(x, f, f, y, stats, rm, rv, n, c, hw, kind, 1e-5, 0.1, act, 0.2, ws, nws, None)
+    for kw in (dict(x=None), dict(y=None), dict(stats=None), dict(n=0), dict(c=0), dict(hw=0), dict(n=-1)):
+        refused(fwd(**kw), b"norm_act_fwd: bad arguments")
+    for kw in (dict(kind=-1), dict(kind=3), dict(act=-1), dict(act=5)):
+        refused(fwd(**kw), b"norm_act_fwd: bad kind / activation")
+    for kw in (dict(kind=1), dict(kind=1, rm=f), dict(kind=1, rv=f)):
+        refused(fwd(**kw), b"norm_act_fwd: eval mode needs the running statistics")
+    for kw in (dict(rm=f), dict(rv=f)):          # kind 0 updates both buffers or none: a lone one would be a write through NULL
+        refused(fwd(**kw), b"norm_act_fwd: running_mean and running_var come together")
+    for kind in (0, 2):
+        for kw in (dict(ws=None), dict(nws=need - 1), dict(nws=0)):
+            refused(fwd(kind=kind, **kw), b"norm_act_fwd: workspace too small", -3)
+    # ---- mmif_norm_act_bwd(x, y, gy, stats, gamma, dx, dgamma, dbeta, n, c, hw, kind, act, slope, ws, bytes, stream)
+    def bwd(x=f, y=f, gy=f, stats=f, dx=f, n=n, c=c, hw=hw, kind=0, act=1, ws=ws, nws=nws):
+        return lambda: lib.mmif_norm_act_bwd(x, y, gy, stats, None, dx, None, None, n, c, hw, kind, act, 0.2, ws, nws, None)
+    for kw in (dict(x=None), dict(y=None), dict(gy=None), dict(stats=None), dict(dx=None), dict(n=0), dict(c=0), dict(hw=0)):
+        refused(bwd(**kw), b"norm_act_bwd: bad arguments")
+    for kw in (dict(kind=-1), dict(kind=3), dict(act=-1), dict(act=5)):
+        refused(bwd(**kw), b"norm_act_bwd: bad kind / activation")
+    for kind in (0, 1, 2):
+        for kw in (dict(ws=None), dict(nws=need - 1)):
+            refused(bwd(kind=kind, **kw), b"norm_act_bwd: workspace too small", -3)
+    # ---- mmif_bn_moments(x, chan_sums, n, c, hw, ws, bytes, stream)
+    for a in ((None, f, n, c, hw), (f, None, n, c, hw), (f, f, 0, c, hw), (f, f, n, 0, hw), (f, f, n, c, 0)):
+        refused(lambda: lib.mmif_bn_moments(*a, ws, nws, None), b"bn_moments: bad arguments")
+    for w_, nb in ((None, nws), (ws, need - 1)):
+        refused(lambda: lib.mmif_bn_moments(f, f, n, c, hw, w_, nb, None), b"bn_moments: workspace too small", -3)
+    # ---- mmif_bn_apply_fwd(x, chan_sums, gamma, beta, y, stats, running_mean, running_var, n, c, hw, eps, momentum, act, slope, stream)
+    def apply_fwd(x=f, chan=f, y=f, stats=f, rm=None, rv=None, n=n, c=c, hw=hw, act=1):
+        return lambda: lib.mmif_bn_apply_fwd(x, chan, None, None, y, stats, rm, rv, n, c, hw, 1e-5, 0.1, act, 0.2, None)
+    for kw in (dict(x=None), dict(chan=None), dict(y=None), dict(stats=None), dict(n=0), dict(c=0), dict(hw=0)):
+        refused(apply_fwd(**kw), b"bn_apply_fwd: bad arguments")
+    for act in (-1, 5):
+        refused(apply_fwd(act=act), b"bn_apply_fwd: bad activation")
+    for kw in (dict(rm=f), dict(rv=f)):
+        refused(apply_fwd(**kw), b"bn_apply_fwd: running_mean and running_var come together")
+    # ---- mmif_bn_bwd_sums(x, y, gy, stats, chan_sums, dgamma, dbeta, n, c, hw, act, slope, ws, bytes, stream)
+    def bwd_sums(x=f, y=f, gy=f, stats=f, chan=f, n=n, c=c, hw=hw, act=1, ws=ws, nws=nws):
+        return lambda: lib.mmif_bn_bwd_sums(x, y, gy, stats, chan, None, None, n, c, hw, act, 0.2, ws, nws, None)
+    for kw in (dict(x=None), dict(y=None), dict(gy=None), dict(stats=None), dict(chan=None), dict(n=0), dict(c=0), dict(hw=0)):
+        refused(bwd_sums(**kw), b"bn_bwd_sums: bad arguments")
+    for act in (-1, 5):
+        refused(bwd_sums(act=act), b"bn_bwd_sums: bad activation")
+    for kw in (dict(ws=None), dict(nws=need - 1)):
+        refused(bwd_sums(**kw), b"bn_bwd_sums: workspace too small", -3)
+    # ---- mmif_bn_apply_bwd(x, y, gy, stats, gamma, chan_sums, count, dx, n, c, hw, act, slope, stream)
+    def apply_bwd(x=f, y=f, gy=f, stats=f, chan=f, count=f, dx=f, n=n, c=c, hw=hw, act=1):
+        return lambda: lib.mmif_bn_apply_bwd(x, y, gy, stats, None, chan, count, dx, n, c, hw, act, 0.2, None)
+    for kw in (dict(x=None), dict(y=None), dict(gy=None), dict(stats=None), dict(chan=None), dict(count=None), dict(dx=None), dict(n=0), dict(c=0),
+               dict(hw=0)):
+        refused(apply_bwd(**kw), b"bn_apply_bwd: bad arguments")
+    for act in (-1, 5):
+        refused(apply_bwd(act=act), b"bn_apply_bwd: bad activation")
+    # ---- mmif_act_fwd(x, y, count, act, slope, stream), mmif_act_bwd(gy, y, dx, count, act, slope, stream); count 0 is accepted and does nothing
+    for a in ((None, f, 4, 1), (f, None, 4, 1), (f, f, -1, 1), (f, f, 4, -1), (f, f, 4, 5)):
+        refused(lambda: lib.mmif_act_fwd(*a, 0.2, None), b"act_fwd: bad arguments")
+    for a in ((None, f, f, 4, 1), (f, None, f, 4, 1), (f, f, None, 4, 1), (f, f, f, -1, 1), (f, f, f, 4, -1), (f, f, f, 4, 5)):
+        refused(lambda: lib.mmif_act_bwd(*a, 0.2, None), b"act_bwd: bad arguments")
+    assert lib.mmif_act_fwd(f, f, 0, 3, 0.2, None) == 0 and lib.mmif_act_bwd(f, f, f, 0, 3, 0.2, None) == 0
+    # ---- mmif_clip_adam_step(params, grads, exp_avg, exp_avg_sq, numel, lr, b1, b2, eps, step, max_norm, grad_scale, norm_out, ws, bytes, stream)
+    aneed = lib.mmif_clip_adam_workspace(16)
+
+    def adam(p=f, g=f, m=f, v=f, numel=16, step=1, ws=ws, nws=nws):
+        return lambda: lib.mmif_clip_adam_step(p, g, m, v, numel, 1e-4, 0.9, 0.999, 1e-8, step, 5.0, 1.0, None, ws, nws, None)
+    refused(adam(numel=0), b"clip_adam_step: numel=0 step=1")
+    refused(adam(numel=-3), b"clip_adam_step: numel=-3 step=1")
+    refused(adam(step=0), b"clip_adam_step: numel=16 step=0")
+    for kw in (dict(p=None), dict(g=None), dict(m=None), dict(v=None)):
+        refused(adam(**kw), b"clip_adam_step: params, grads, exp_avg and exp_avg_sq must not be NULL")
+    for kw in (dict(nws=aneed - 1), dict(nws=0), dict(ws=None, nws=0)):
+        refused(adam(**kw), b"clip_adam_step: workspace too small", -3)
+    refused(adam(ws=None), b"clip_adam_step: workspace is NULL")          # enough bytes claimed, no buffer behind them
+
+
 @pytest.mark.parametrize("name", ["PFNetv1", "PFNetv2", "DenseFuse", "VIFNet", "NestFuse", "RFNNest", "DeepFuse", "DBNet", "SEDRFuse", "IFCNN",
                                   "DIFNet", "PMGI", "UNFusion", "MAFusion", "Res2Fusion"])
 def test_state_dict_manifest_and_init(name):
