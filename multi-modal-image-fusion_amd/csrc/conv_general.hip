@@ -631,6 +631,7 @@ extern "C" int mmif_dwconv_dgrad(const float* gy, const float* w, float* dx, int
                                  int32_t reflect, void* stream) {
     MMIF_REQUIRE(gy != nullptr && w != nullptr && dx != nullptr && n > 0 && c > 0 && h > 0 && wd > 0, "dwconv_dgrad: bad arguments");
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "dwconv_dgrad: ksize must be 1 or 3 (got %d)", ksize);
+    MMIF_REQUIRE(!reflect || ksize == 1 || (h >= 2 && wd >= 2), "dwconv_dgrad: reflect padding needs h,w >= 2");
     hipLaunchKernelGGL(dwconv_dgrad_kernel, dim3(grid1d((long long)n * c * h * wd)), dim3(256), 0, (hipStream_t)stream, gy, w, dx, (long long)n * c,
                        c, h, wd, ksize, reflect);
     return check_launch("dwconv_dgrad");
@@ -640,6 +641,7 @@ extern "C" int mmif_dwconv_wgrad(const float* x, const float* gy, float* dw, flo
                                  int32_t reflect, void* stream) {
     MMIF_REQUIRE(x != nullptr && gy != nullptr && dw != nullptr && n > 0 && c > 0 && h > 0 && wd > 0, "dwconv_wgrad: bad arguments");
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "dwconv_wgrad: ksize must be 1 or 3 (got %d)", ksize);
+    MMIF_REQUIRE(!reflect || ksize == 1 || (h >= 2 && wd >= 2), "dwconv_wgrad: reflect padding needs h,w >= 2");
     hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3(c), dim3(256), 0, (hipStream_t)stream, x, gy, dw, db, n, c, h, wd, ksize, reflect);
     return check_launch("dwconv_wgrad");
 }

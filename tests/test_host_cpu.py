@@ -118,9 +118,29 @@ def test_c_abi_validation_of_the_widened_entry_points_without_gpu():
     assert lib.mmif_gconv_dgrad_workspace(2, 8, 16, 16, 2, 1) == 2 * 8 * 20 * 20 * 4 and lib.mmif_gconv_dgrad_workspace(2, 8, 16, 16, 2, 0) == 0
     assert lib.mmif_gconv_wgrad(f, f, f, None, 1, 8, 8, 16, 16, 5, 1, 2, 1, f, 64, None) == -3
     assert lib.mmif_gconvt_fwd(f, f, None, f, 1, 8, 8, 4, 4, 3, 2, 1, 2, 0, None) == -1           # output_padding >= stride
+    # depth-wise reflect padding by 1 has no source below 2 x 2: the forward and both gradients refuse it alike (k = 1 pads nothing)
+    for h, wd in ((1, 4), (4, 1), (1, 1)):
+        for call, what in ((lambda: lib.mmif_dwconv_fwd(f, f, None, f, 1, 1, h, wd, 3, 1, None), b"dwconv_fwd"),
+                           (lambda: lib.mmif_dwconv_dgrad(f, f, f, 1, 1, h, wd, 3, 1, None), b"dwconv_dgrad"),
+                           (lambda: lib.mmif_dwconv_wgrad(f, f, f, None, 1, 1, h, wd, 3, 1, None), b"dwconv_wgrad")):
+            assert call() == -1
+            assert what + b": reflect padding needs h,w >= 2" in lib.mmif_last_error()
+    assert lib.mmif_dwconv_dgrad(f, f, f, 1, 1, 4, 4, 5, 1, None) == -1 and b"dwconv_dgrad: ksize must be 1 or 3" in lib.mmif_last_error()
+    assert lib.mmif_dwconv_wgrad(f, f, f, None, 1, 1, 4, 4, 2, 0, None) == -1 and b"dwconv_wgrad: ksize must be 1 or 3" in lib.mmif_last_error()
     assert lib.mmif_relu_bwd(None, f, f, 4, None) == -1 and lib.mmif_channel_sum(f, f, 0, 1, 1, None) == -1
     assert lib.mmif_reflect_pad_fwd(f, f, 1, 4, 4, 4, 0, 0, 0, None) == -1      # padding must be smaller than the input
     assert lib.mmif_maxpool_nchw_fwd(f, f, f, 1, 3, 8, 4, None) == -1 and lib.mmif_nearest_up_fwd(f, f, 1, 2, 2, 0, None) == -1
+    # each plane-wise resampler and its backward refuse the same geometries
+    for fwd, bwd, bad in ((lambda *a: lib.mmif_bilinear_up_fwd(f, f, *a, None), lambda *a: lib.mmif_bilinear_up_bwd(f, f, *a, None),
+                           ((1, 4, 4, 3, 4), (1, 4, 4, 4, 3), (0, 2, 2, 2, 2), (1, 0, 2, 2, 2))),
+                          (lambda *a: lib.mmif_maxpool_nchw_fwd(f, f, f, *a, None), lambda *a: lib.mmif_maxpool_nchw_bwd(f, f, f, *a, None),
+                           ((1, 3, 8, 4), (1, 8, 3, 4), (1, 16, 16, 16), (1, 4, 4, 0), (0, 4, 4, 2))),
+                          (lambda *a: lib.mmif_nearest_up_fwd(f, f, *a, None), lambda *a: lib.mmif_nearest_up_bwd(f, f, *a, None),
+                           ((1, 2, 2, 0), (0, 2, 2, 2), (1, 0, 2, 2))),
+                          (lambda *a: lib.mmif_reflect_pad_fwd(f, f, *a, None), lambda *a: lib.mmif_reflect_pad_bwd(f, f, *a, None),
+                           ((1, 4, 4, 4, 0, 0, 0), (1, 4, 4, 0, 0, 0, 4), (1, 4, 4, -2, -2, 0, 0), (1, 4, 4, 0, 0, -4, 0), (0, 4, 4, 1, 1, 1, 1)))):
+        for a in bad:
+            assert fwd(*a) == -1 and bwd(*a) == -1, a
     from mmif._lib import MmifPackJob
     jobs = (MmifPackJob * 1)()
     assert lib.mmif_pack_weights_multi(jobs, 0, None) == -1
