@@ -158,6 +158,22 @@ int mmif_dwconv_dgrad(const float* gy, const float* w, float* dx, int32_t n, int
                       int32_t reflect, void* stream);
 int mmif_dwconv_wgrad(const float* x, const float* gy, float* dw, float* db, int32_t n, int32_t c, int32_t h, int32_t wd,
                       int32_t ksize, int32_t reflect, void* stream);
+/* mixed depth-wise conv (MixConvBlock.dwconvs core/block.py:249-273; a lone 5x5 / 7x7 depth-wise ConvLayer is nseg == 1): x, y, gy, dx
+ * [n][nseg * c][h][wd] fp32 NCHW.  Segment i = channels [i c, (i + 1) c) has kernel k_i = k0 + 2 i, stride 1, padding k_i / 2 (reflect without
+ * edge repeat, or zeros).  Legal: k0 odd, 1 <= nseg <= 4, k0 + 2 (nseg - 1) <= 7, and with reflect padding h, wd >= kmax / 2 + 1; anything else
+ * returns MMIF_EINVAL before any launch (the workspace query returns 0).  w, dw: ONE packed buffer, segment i at float offset
+ * c sum_{j<i} k_j^2 with layout [c][k_i][k_i]; bias, db: [nseg * c] or NULL.
+ *   fwd    y = bias + sum_{u,v} w[u][v] x[R(yy + u - p)][R(xx + v - p)]   (zero padding: taps outside the plane contribute 0)
+ *   dgrad  the exact adjoint: a pixel within p of an edge also collects its mirror images
+ *   wgrad  dw[ch][u][v] = sum_{n, pixels} gy x[R(..)], db = sum gy; two stages in a fixed order, no atomics, grids that depend on the shape
+ *          only: bit-identical from run to run and device to device.  workspace: mmif_mixdw_wgrad_workspace bytes (MMIF_EWORKSPACE if smaller) */
+int mmif_mixdw_fwd(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c, int32_t nseg, int32_t k0, int32_t h,
+                   int32_t wd, int32_t reflect, void* stream);
+int mmif_mixdw_dgrad(const float* gy, const float* w, float* dx, int32_t n, int32_t c, int32_t nseg, int32_t k0, int32_t h, int32_t wd,
+                     int32_t reflect, void* stream);
+size_t mmif_mixdw_wgrad_workspace(int32_t n, int32_t c, int32_t nseg, int32_t k0, int32_t h, int32_t wd);
+int mmif_mixdw_wgrad(const float* x, const float* gy, float* dw, float* db, int32_t n, int32_t c, int32_t nseg, int32_t k0, int32_t h,
+                     int32_t wd, int32_t reflect, void* workspace, size_t workspace_bytes, void* stream);
 /* depth-wise patch conv (groups == channels, kernel == stride == s in [2, 16], padding 0; Attention.pool core/block.py:404-412 and
  * TransitionBlock(down_mode='stride') :645-654): x, dx [n][c][h][wd]; y, gy [n][c][h / s][wd / s]; w [c][1][s][s]; h, wd >= s.
  * dgrad writes exactly 0 into the rows and columns beyond floor(h / s) s and floor(wd / s) s.  wgrad runs two stages in a fixed order

@@ -16,14 +16,23 @@ import torch.distributed as dist
 
 from data.transform import denorm, norm
 
-__all__ = ['get_train_args', 'get_test_args', 'save_result', 'setup_seed', 'setup_dist', 'reduce_value', 'AverageMeter',
+__all__ = ['get_train_args', 'get_test_args', 'build_model', 'save_result', 'setup_seed', 'setup_dist', 'reduce_value', 'AverageMeter',
            'WarmupLR', 'Logger', 'make_logger', 'norm', 'denorm']
 
 
 # flag tables: (name, default, type, help).  The reference's flags (common.py:23-71) keep their names, defaults and -- including the
 # `type=bool` ones, which treat any non-empty string as True -- their argparse behaviour; the last four are this engine's additions
 # (the reference picks model / precision by editing the scripts).
-_MODELS = 'PFNetv1 | PFNetv2 | DenseFuse | VIFNet | NestFuse | RFNNest | DeepFuse | DBNet | SEDRFuse | IFCNN | DIFNet | PMGI | UNFusion | MAFusion | Res2Fusion'
+_MODELS = 'PFNetv1 | PFNetv2 | DenseFuse | VIFNet | NestFuse | RFNNest | DeepFuse | DBNet | SEDRFuse | IFCNN | DIFNet | PMGI | UNFusion | MAFusion | Res2Fusion | MyFusion'
+_ENCODERS = ('SepConvBlock', 'MixConvBlock', 'Res2ConvBlock', 'ConvFormerBlock', 'MixFormerBlock', 'Res2FormerBlock', 'TransformerBlock')
+_DECODERS = ('Decoder', 'LSDecoder', 'NestDecoder', 'FSDecoder')
+# MyFusion's constructor arguments (reference core/model.py:631-641; the defaults are the constructor's)
+_MYFUSION = [('encoder', 'SepConvBlock', str, 'MyFusion: one encoder block for all four levels, or four comma-separated ones: ' + ' | '.join(_ENCODERS)),
+             ('decoder', 'NestDecoder', str, 'MyFusion: ' + ' | '.join(_DECODERS)),
+             ('fusion_method', 'attn', str, 'MyFusion: elem | attn | concat | rfn'),
+             ('fusion_mode', 'sca', str, "MyFusion: sum | mean | max for 'elem', sa | ca | sca | wavg for 'attn'"),
+             ('down_mode', 'stride', str, 'MyFusion: stride | maxpool'), ('up_mode', 'bilinear', str, 'MyFusion: bilinear | nearest'),
+             ('share_weight_levels', 4, int, 'MyFusion: how many pyramid levels, counted from the deepest, the two inputs share (0..4)')]
 _EXTRA = [('model', 'PFNetv1', str, _MODELS),
           ('dtype', 'fp32', str, 'feature-map storage: fp32 (parity) | bf16 (throughput)'),
           ('synthetic', 0, int, '>0: train on this many synthetic random pairs (no dataset needed)'),
@@ -36,19 +45,38 @@ _TEST = [('use_gpu', True, bool, 'enable to test on gpu'), ('data', 'roadscene',
          ('ckpt', '2023-02-26_23-15', str, 'checkpoint folder name')]
 
 
-def _parse(description, table):
+def _parse(description, table, argv=None):
     ap = argparse.ArgumentParser(description=description)
-    for name, default, kind, text in table + _EXTRA:
+    for name, default, kind, text in table + _EXTRA + _MYFUSION:
         ap.add_argument('--' + name, default=default, type=kind, help=text)
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
-def get_train_args():
-    return _parse('Training', _TRAIN)
+def get_train_args(argv=None):
+    return _parse('Training', _TRAIN, argv)
 
 
-def get_test_args():
-    return _parse('Testing', _TEST)
+def get_test_args(argv=None):
+    return _parse('Testing', _TEST, argv)
+
+
+def build_model(args):
+    """the model --model names (on the CPU; the caller moves it): zero-argument constructors, except MyFusion, which takes its flags"""
+    import core.block as B
+    import core.model as M
+    names = [n.strip() for n in _MODELS.split('|')]
+    if args.model not in names:
+        raise ValueError(f'--model must be one of {_MODELS} (got {args.model!r})')
+    if args.model != 'MyFusion':
+        return getattr(M, args.model)()
+    enc = [e.strip() for e in args.encoder.split(',')]
+    if len(enc) not in (1, 4) or any(e not in _ENCODERS for e in enc):
+        raise ValueError(f'--encoder takes one name or four comma-separated names of {_ENCODERS} (got {args.encoder!r})')
+    if args.decoder not in _DECODERS:
+        raise ValueError(f'--decoder must be one of {_DECODERS} (got {args.decoder!r})')
+    enc = [getattr(B, e) for e in enc]
+    return M.MyFusion(encoder=enc[0] if len(enc) == 1 else enc, decoder=getattr(B, args.decoder), fusion_method=args.fusion_method,
+                      fusion_mode=args.fusion_mode, down_mode=args.down_mode, up_mode=args.up_mode, share_weight_levels=args.share_weight_levels)
 
 
 def save_result(pred, img1=None, img2=None):

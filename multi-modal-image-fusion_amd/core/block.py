@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Network blocks -- API mirror of the reference's core/block.py for the hot-path blocks
-(ConvLayer :26-118, DenseBlock :137-151, Attention :355-434, MetaFormerBlock and its sub-classes :503-617, ConvBlock :708-722, RFN :737-759, NestDecoder :836-867,
+(ConvLayer :26-118, DenseBlock :137-151, MixConvBlock :229-283, DCBlock :667-705, Decoder / LSDecoder :800-833, Attention :355-434, MetaFormerBlock and its sub-classes :503-617, ConvBlock :708-722, RFN :737-759, NestDecoder :836-867,
 Upsample/Downsample :941-991), executed by hand-written HIP kernels.
 
 Called standalone (NCHW tensors in / out) every block converts at its boundary; inside the models
@@ -19,9 +19,9 @@ from mmif.tensor import BT
 
 from .fusion import concat_fusion, element_fusion
 
-__all__ = ['ConvLayer', 'ResBlock', 'DenseBlock', 'SepConvBlock', 'Res2ConvBlock', 'Attention', 'FFN', 'Scale', 'LayerNorm', 'BatchNorm2d', 'MetaFormerBlock',
-           'ConvFormerBlock', 'Res2FormerBlock', 'TransformerBlock', 'TransitionBlock', 'ConvBlock', 'ECB', 'DCB', 'RFN', 'NestEncoder', 'NestDecoder', 'FSDecoder',
-           'Downsample', 'Upsample', 'MaxPool2d']
+__all__ = ['ConvLayer', 'ResBlock', 'DenseBlock', 'SepConvBlock', 'MixConvBlock', 'Res2ConvBlock', 'Attention', 'FFN', 'Scale', 'LayerNorm', 'BatchNorm2d',
+           'MetaFormerBlock', 'ConvFormerBlock', 'MixFormerBlock', 'Res2FormerBlock', 'TransformerBlock', 'TransitionBlock', 'DCBlock', 'ConvBlock', 'ECB', 'DCB',
+           'RFN', 'NestEncoder', 'Decoder', 'LSDecoder', 'NestDecoder', 'FSDecoder', 'Downsample', 'Upsample', 'MaxPool2d']
 
 
 class _ConvLayerFn(torch.autograd.Function):
@@ -179,6 +179,37 @@ class _DwConvFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _MixDwFn(torch.autograd.Function):
+    """mixed depth-wise conv on csrc/mixdw.hip: the UN-chunked tensor of nseg * c channels, segment i through its own depth-wise
+    k_i = k0 + 2 i conv (stride 1, padding k_i / 2), the result written in place of the concatenation -- MixConvBlock.dwconvs in one launch
+    per direction; nseg == 1 is a lone 5 x 5 / 7 x 7 depth-wise ConvLayer.  params = the nseg weights [c, 1, k_i, k_i], then the nseg biases
+    (all of them or none)."""
+
+    @staticmethod
+    def forward(ctx, x, k0, reflect, nseg, *params):
+        T.require_device(x, "ConvLayer input")
+        ws, bs = params[:nseg], params[nseg:]
+        xd = x.detach().contiguous().float()
+        wp = torch.cat([w.detach().reshape(-1) for w in ws]).float() if nseg > 1 else ws[0].detach().reshape(-1).contiguous().float()
+        bp = None
+        if bs:
+            bp = torch.cat([b.detach() for b in bs]).float() if nseg > 1 else bs[0].detach().contiguous().float()
+        ctx.saved = (xd, wp)
+        ctx.meta = (k0, reflect, nseg, [tuple(w.shape) for w in ws], bool(bs))
+        return T.mixdw_fwd(xd, wp, bp, nseg, k0, reflect)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xd, wp = ctx.saved
+        k0, reflect, nseg, shapes, has_bias = ctx.meta
+        gy = gy.contiguous().float()
+        dwp, dbp = T.mixdw_wgrad(xd, gy, nseg, k0, reflect, has_bias)
+        dx = T.mixdw_dgrad(gy, wp, nseg, k0, reflect) if ctx.needs_input_grad[0] else None
+        dws = [d.reshape(sh) for d, sh in zip(torch.split(dwp, [sh[0] * sh[2] * sh[3] for sh in shapes]), shapes)]
+        dbs = list(torch.chunk(dbp, nseg)) if has_bias else []
+        return (dx, None, None, None, *dws, *dbs)
+
+
 class _PatchConvFn(torch.autograd.Function):
     """depth-wise nn.Conv2d with kernel == stride in 2..16 and padding 0 (groups == channels) on csrc/conv_general.hip -- Attention.pool,
     TransitionBlock(down_mode='stride')"""
@@ -296,6 +327,10 @@ class ConvLayer(nn.Module):
         depthwise = groups > 1 and groups == in_ch == out_ch and layer is nn.Conv2d and stride == 1 and ksize in (1, 3) and padding == ksize // 2
         # depth-wise patch conv: kernel == stride, no padding (Attention.pool, TransitionBlock(down_mode='stride'))
         patch = groups > 1 and groups == in_ch == out_ch and layer is nn.Conv2d and ksize == stride and 2 <= ksize <= 16 and padding == 0
+        # depth-wise 5 x 5 / 7 x 7 (MixConvBlock.dwconvs): the tiled kernels of csrc/mixdw.hip, one segment
+        self._dw_wide = (groups > 1 and groups == in_ch == out_ch and layer is nn.Conv2d and stride == 1 and ksize in (5, 7) and padding == ksize // 2
+                         and padding_mode in ('reflect', 'zeros'))
+        depthwise = depthwise or self._dw_wide
         epi_ok = (pre_norm is None and norm in (None, nn.BatchNorm2d, nn.GroupNorm) and act in _ACT_CODE and dilation == 1
                   and (groups == 1 or depthwise or patch))
         self._epilogue = epi_ok and (norm is not None or act in (nn.LeakyReLU, nn.Tanh, nn.ReLU6) or depthwise or patch)
@@ -317,6 +352,8 @@ class ConvLayer(nn.Module):
 
     def _conv(self, x, relu):
         conv = self.layers[0]
+        if self._dw_wide:
+            return _MixDwFn.apply(x, conv.kernel_size[0], self._geom[2], 1, conv.weight, *(() if conv.bias is None else (conv.bias, )))
         if self._depthwise:
             return _DwConvFn.apply(x, conv.weight, conv.bias, self._geom[2])
         if self._patch:
@@ -401,6 +438,33 @@ class SepConvBlock(nn.Module):
         if self.residual:
             out = element_fusion(out, self.shortcut(x), 'sum')
         return self._finish(out)
+
+
+class MixConvBlock(SepConvBlock):
+    """reference core/block.py:229-283 (MixConv): the expanded features are split into `scale` groups of in_ch channels, group i goes through
+    a depth-wise (2 i + 1) x (2 i + 1) conv, and the groups are concatenated again.  With scale <= 4 and no norm on the depth-wise layers that
+    is ONE launch of csrc/mixdw.hip on the un-chunked tensor (no chunk copies, no concatenation); otherwise the layers run one by one."""
+
+    def __init__(self, in_ch, out_ch, scale=4, bias=False, norm=None, act=nn.ReLU6, residual=True, attention=False):
+        super(MixConvBlock, self).__init__(in_ch, out_ch, scale=scale, bias=bias, norm=norm, act=act, residual=residual, attention=attention)
+        width = in_ch
+        self.dwconvs = nn.ModuleList([ConvLayer(width, width, ksize=2 * i + 1, groups=width, bias=bias, norm=norm, act=None) for i in range(scale)])
+        self._fused = scale <= 4 and norm is None
+
+    def _mix_layers(self, x):
+        """the reference's per-layer path on an already expanded tensor"""
+        xs = torch.chunk(x, self.scale, dim=1)
+        if self.scale == 1:
+            return self.dwconvs[0](xs[0])
+        return concat_fusion([self.dwconvs[i](xs[i].contiguous()) for i in range(self.scale)])
+
+    def _mix(self, x):
+        x = self.pwconv1(x)
+        if not (self._fused and x.is_cuda):
+            return self._mix_layers(x)
+        convs = [d.layers[0] for d in self.dwconvs]
+        biases = [c.bias for c in convs if c.bias is not None]
+        return _MixDwFn.apply(x, 1, any(d._geom[2] for d in self.dwconvs), self.scale, *[c.weight for c in convs], *biases)
 
 
 class Res2ConvBlock(SepConvBlock):
@@ -649,6 +713,14 @@ class ConvFormerBlock(MetaFormerBlock):
         self.token_mixer = SepConvBlock(in_ch, out_ch, residual=True, attention=False)
 
 
+class MixFormerBlock(MetaFormerBlock):
+    """reference core/block.py:563-580"""
+
+    def __init__(self, in_ch, out_ch, norm_layer=nn.BatchNorm2d, act_layer=nn.ReLU6, layer_scale=None, res_scale=None):
+        super(MixFormerBlock, self).__init__(in_ch, out_ch, norm_layer=norm_layer, act_layer=act_layer, layer_scale=layer_scale, res_scale=res_scale)
+        self.token_mixer = MixConvBlock(in_ch, out_ch, residual=True, attention=False)
+
+
 class Res2FormerBlock(MetaFormerBlock):
     """reference core/block.py:583-600"""
 
@@ -679,6 +751,30 @@ class TransitionBlock(nn.Module):
 
     def forward(self, x):
         return self.layers(x)
+
+
+class DCBlock(nn.Module):
+    """reference core/block.py:667-705 (MyFusion's decoder block): point-wise halve -> depth-wise 3 x 3 -> point-wise project, optional
+    (projected) residual, activation at the end"""
+
+    def __init__(self, in_ch, out_ch, bias=False, norm=None, act=nn.ReLU6, residual=False):
+        super(DCBlock, self).__init__()
+        self.residual = residual
+        self.in_ch, self.out_ch = in_ch, out_ch
+        hid_ch = in_ch // 2
+        self.layers = nn.Sequential(ConvLayer(in_ch, hid_ch, ksize=1, bias=bias, norm=norm, act=act),
+                                    ConvLayer(hid_ch, hid_ch, ksize=3, groups=hid_ch, bias=bias, norm=norm, act=act),
+                                    ConvLayer(hid_ch, out_ch, ksize=1, bias=bias, norm=norm, act=None))
+        if residual:
+            self.shortcut = ConvLayer(in_ch, out_ch, ksize=1, bias=bias, norm=norm, act=None) if in_ch != out_ch else nn.Identity()
+        self.act = act()
+        self._act_code = _ACT_CODE.get(act)
+
+    def forward(self, x):
+        out = self.layers(x)
+        if self.residual:
+            out = element_fusion(out, self.shortcut(x), 'sum')
+        return _ActFn.apply(out, self._act_code) if (self._act_code is not None and out.is_cuda) else self.act(out)
 
 
 class DenseBlock(nn.Module):
@@ -847,6 +943,38 @@ class Upsample(_Resample):
 
     def _nearest_op(self, feat):
         return _NearestUpFn.apply(feat, int(self.up.scale_factor)) if feat.is_cuda else self.up(feat)
+
+
+class Decoder(nn.Module):
+    """reference core/block.py:800-814: a plain top-down decoder -- it reads the deepest level only"""
+
+    def __init__(self, block, num_ch, up_mode='bilinear'):
+        super(Decoder, self).__init__()
+        self.DB1 = block(num_ch[1], num_ch[0])
+        self.DB2 = block(num_ch[2], num_ch[1])
+        self.DB3 = block(num_ch[3], num_ch[2])
+        self.up = Upsample(up_mode, 2)
+
+    def forward(self, feats):
+        y3 = self.DB3(self.up(feats[3], feats[2].shape))
+        y2 = self.DB2(self.up(y3, feats[1].shape))
+        return self.DB1(self.up(y2, feats[0].shape))
+
+
+class LSDecoder(nn.Module):
+    """reference core/block.py:817-833 (U-Net: long skip connections)"""
+
+    def __init__(self, block, num_ch, up_mode='bilinear'):
+        super(LSDecoder, self).__init__()
+        self.DB1 = block(num_ch[0] + num_ch[1], num_ch[0])
+        self.DB2 = block(num_ch[1] + num_ch[2], num_ch[1])
+        self.DB3 = block(num_ch[2] + num_ch[3], num_ch[2])
+        self.up = Upsample(up_mode, 2)
+
+    def forward(self, feats):
+        y3 = self.DB3(concat_fusion((feats[2], self.up(feats[3], feats[2].shape))))
+        y2 = self.DB2(concat_fusion((feats[1], self.up(y3, feats[1].shape))))
+        return self.DB1(concat_fusion((feats[0], self.up(y2, feats[0].shape))))
 
 
 class NestDecoder(nn.Module):

@@ -13,7 +13,8 @@ from .block import *
 from .fusion import *
 
 __all__ = ['PFNetv1', 'PFNetv2', 'DenseFuse', 'VIFNet', 'NestFuse', 'RFNNest',                       # the hot-path nets (fused engines)
-           'DeepFuse', 'DBNet', 'SEDRFuse', 'UNFusion', 'Res2Fusion', 'MAFusion', 'IFCNN', 'DIFNet', 'PMGI']   # core/zoo.py
+           'DeepFuse', 'DBNet', 'SEDRFuse', 'UNFusion', 'Res2Fusion', 'MAFusion', 'IFCNN', 'DIFNet', 'PMGI',   # core/zoo.py
+           'MyFusion']
 
 
 class _FusionModel(nn.Module):
@@ -190,6 +191,88 @@ class RFNNest(NestFuse):
     def fusion(self, feats1, feats2):
         return (self.RFN1(feats1[0], feats2[0]), self.RFN2(feats1[1], feats2[1]), self.RFN3(feats1[2], feats2[2]),
                 self.RFN4(feats1[3], feats2[3]))
+
+
+class MyFusion(nn.Module):
+    '''The reference author's configurable net (reference core/model.py:630-842): a four-level pyramid of TransitionBlocks and `encoder` blocks
+    (one class, or a list of four) for each input -- the first `share_weight_levels` levels counted from the deepest share their weights between
+    the two inputs -- a fusion per level ('elem' | 'attn' | 'concat' | 'rfn') and a `decoder` of DCBlocks.  Same arguments, defaults, attribute
+    names and state_dict keys.  Runs block by block through autograd: every layer is its own HIP launch, a MixConvBlock's depth-wise stage one
+    launch of csrc/mixdw.hip.'''
+
+    def __init__(self, encoder=SepConvBlock, decoder=NestDecoder, bias=False, norm=None, act=nn.ReLU6, fusion_method='attn', fusion_mode='sca',
+                 down_mode='stride', up_mode='bilinear', share_weight_levels=4):
+        super(MyFusion, self).__init__()
+        num_ch = [16, 32, 64, 128]
+        self.fusion_method, self.fusion_mode = fusion_method, fusion_mode
+        self.down_mode, self.up_mode = down_mode, up_mode
+        self.share_weight_levels = share_weight_levels
+        kw = dict(bias=bias, norm=norm, act=act)
+
+        def branch(tag, levels):
+            # (registration order = the reference's: conv_in, down1 .. down4 of a branch, only the levels it owns)
+            if levels[0]:
+                setattr(self, 'conv_in_' + tag, ConvLayer(1, 8, ksize=1, **kw))
+                setattr(self, 'down1_' + tag, TransitionBlock(8, num_ch[0], stride=1, **kw))
+            for i in (1, 2, 3):
+                if levels[i]:
+                    setattr(self, 'down%d_%s' % (i + 1, tag), TransitionBlock(num_ch[i - 1], num_ch[i], stride=2, down_mode=down_mode, **kw))
+
+        own = [share_weight_levels < 4, share_weight_levels < 3, share_weight_levels < 2, share_weight_levels < 1]
+        branch('1', [True] * 4)
+        branch('2', own)
+        if not isinstance(encoder, list):
+            encoder = [encoder] * 4
+        for i in range(4):
+            setattr(self, 'EB%d_1' % (i + 1), encoder[i](num_ch[i], num_ch[i]))
+        for i in range(4):
+            if own[i]:
+                setattr(self, 'EB%d_2' % (i + 1), encoder[i](num_ch[i], num_ch[i]))
+        if fusion_method == 'elem':
+            assert fusion_mode in ['sum', 'mean', 'max']
+        elif fusion_method == 'attn':
+            assert fusion_mode in ['sa', 'ca', 'sca', 'wavg']
+        elif fusion_method == 'concat':
+            for i in range(4):
+                setattr(self, 'fuse%d' % (i + 1), ConvLayer(num_ch[i] * 2, num_ch[i], act=None))
+        elif fusion_method == 'rfn':
+            for i in range(4):
+                setattr(self, 'RFN%d' % (i + 1), RFN(num_ch[i]))
+        self.decode = decoder(DCBlock, num_ch, up_mode)
+        self.conv_out = ConvLayer(num_ch[0], 1, ksize=1, **kw)
+
+    def _pyramid(self, img, tags):
+        x, feats = img, []
+        for i, t in enumerate(tags):
+            if i == 0:
+                x = getattr(self, 'conv_in_' + t)(x)
+            x = getattr(self, 'EB%d_%s' % (i + 1, t))(getattr(self, 'down%d_%s' % (i + 1, t))(x))
+            feats.append(x)
+        return tuple(feats)
+
+    def encoder(self, img1, img2):
+        if self.share_weight_levels not in (0, 1, 2, 3, 4):   # (the reference leaves x1_2 unbound here: UnboundLocalError)
+            raise UnboundLocalError("share_weight_levels must be 0..4")
+        own = 4 - self.share_weight_levels   # the second input's own levels: the first `own`
+        return self._pyramid(img1, '1111'), self._pyramid(img2, '2' * own + '1' * (4 - own))
+
+    def fusion(self, feats1, feats2):
+        if self.fusion_method == 'elem':
+            return tuple(element_fusion(a, b, self.fusion_mode) for a, b in zip(feats1, feats2))
+        if self.fusion_method == 'attn':
+            return tuple(attention_fusion(a, b, self.fusion_mode) for a, b in zip(feats1, feats2))
+        if self.fusion_method == 'concat':
+            return tuple(getattr(self, 'fuse%d' % (i + 1))(concat_fusion((a, b))) for i, (a, b) in enumerate(zip(feats1, feats2)))
+        if self.fusion_method == 'rfn':
+            return tuple(getattr(self, 'RFN%d' % (i + 1))(a, b) for i, (a, b) in enumerate(zip(feats1, feats2)))
+        raise ValueError("only supported ['elem', 'attn', 'concat', 'rfn'] method")
+
+    def decoder(self, feats):
+        return self.conv_out(self.decode(feats))
+
+    def forward(self, img1, img2):
+        feats1, feats2 = self.encoder(img1, img2)
+        return self.decoder(self.fusion(feats1, feats2))
 
 
 # the other classic models (scope row n4: layer by layer on the general HIP kernels) live in core/zoo.py; they subclass the bases above

@@ -906,6 +906,46 @@ def dwconv_wgrad(x, gy, k, reflect, want_bias):
     return dw, db
 
 
+# ------------------------------------------------------------------ mixed depth-wise conv (csrc/mixdw.hip): nseg segments of c channels, k_i = k0 + 2 i
+def mixdw_packed_numel(c, nseg, k0):
+    return c * sum((k0 + 2 * i) ** 2 for i in range(nseg))
+
+
+def mixdw_fwd(x, w, bias, nseg, k0, reflect):
+    """x [N, nseg * c, H, W]; w: the packed weights (segment i at c sum_{j<i} k_j^2, [c][k_i][k_i]); bias [nseg * c] or None"""
+    _f32c(x, "x"), _f32c(w, "weight")
+    n, ch, h, wd = x.shape
+    c = ch // nseg
+    assert c * nseg == ch and w.numel() == mixdw_packed_numel(c, nseg, k0) and (bias is None or bias.numel() == ch), "mixdw_fwd: operand sizes"
+    y = torch.empty_like(x)
+    check(lib.mmif_mixdw_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), n, c, nseg, k0, h, wd, int(reflect), stream_ptr()), "mixdw_fwd")
+    return y
+
+
+def mixdw_dgrad(gy, w, nseg, k0, reflect):
+    _f32c(gy, "gy"), _f32c(w, "weight")
+    n, ch, h, wd = gy.shape
+    c = ch // nseg
+    assert c * nseg == ch and w.numel() == mixdw_packed_numel(c, nseg, k0), "mixdw_dgrad: operand sizes"
+    dx = torch.empty_like(gy)
+    check(lib.mmif_mixdw_dgrad(_ptr(gy), _ptr(w), _ptr(dx), n, c, nseg, k0, h, wd, int(reflect), stream_ptr()), "mixdw_dgrad")
+    return dx
+
+
+def mixdw_wgrad(x, gy, nseg, k0, reflect, want_bias):
+    """(dw packed like the weights, db [nseg * c] or None)"""
+    _f32c(x, "x"), _f32c(gy, "gy")
+    n, ch, h, wd = x.shape
+    c = ch // nseg
+    assert c * nseg == ch and gy.shape == x.shape, "mixdw_wgrad: operand sizes"
+    dw = torch.empty(mixdw_packed_numel(c, nseg, k0), dtype=torch.float32, device=x.device)
+    db = torch.empty(ch, dtype=torch.float32, device=x.device) if want_bias else None
+    ws = torch.empty(lib.mmif_mixdw_wgrad_workspace(n, c, nseg, k0, h, wd) // 4 + 1, dtype=torch.float32, device=x.device)
+    check(lib.mmif_mixdw_wgrad(_ptr(x), _ptr(gy), _ptr(dw), _ptr(db), n, c, nseg, k0, h, wd, int(reflect), _ptr(ws), ws.numel() * 4, stream_ptr()),
+          "mixdw_wgrad")
+    return dw, db
+
+
 # ------------------------------------------------------------------ resampling glue on NCHW fp32 (max-pool, nearest up-sampling, reflect pad / crop)
 def maxpool_nchw_fwd(x, k):
     _f32c(x, "x")

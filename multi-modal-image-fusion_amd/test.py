@@ -30,7 +30,7 @@ from mmif import engine as E
 device = torch.device('cuda:0' if torch.cuda.is_available() else 'cpu')
 MODELS = {'PFNetv1': PFNetv1, 'PFNetv2': PFNetv2, 'DenseFuse': DenseFuse, 'VIFNet': VIFNet, 'NestFuse': NestFuse, 'RFNNest': RFNNest,
           'DeepFuse': DeepFuse, 'DBNet': DBNet, 'SEDRFuse': SEDRFuse, 'IFCNN': IFCNN, 'DIFNet': DIFNet, 'PMGI': PMGI,
-          'UNFusion': UNFusion, 'MAFusion': MAFusion, 'Res2Fusion': Res2Fusion}
+          'UNFusion': UNFusion, 'MAFusion': MAFusion, 'Res2Fusion': Res2Fusion, 'MyFusion': MyFusion}
 
 
 def _sync():
@@ -95,7 +95,7 @@ if __name__ == '__main__':
         test_loader = DataLoader(test_set, batch_size=1, shuffle=False, num_workers=4, pin_memory=True)
 
     print(f'model: {args.model}')
-    model = MODELS[args.model]().to(device, non_blocking=True)
+    model = build_model(args).to(device, non_blocking=True)
     params = sum([param.numel() for param in model.parameters()])
     print(f'params: {params / 1e6:.3f}M')
     if os.path.isfile(ckpt_path):

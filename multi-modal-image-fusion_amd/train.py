@@ -176,8 +176,7 @@ if __name__ == '__main__':
         os.makedirs(valid_save_dir, exist_ok=True)
     train_loader, valid_loader, train_sampler = make_loaders()
 
-    model = {'PFNetv1': PFNetv1, 'PFNetv2': PFNetv2, 'DenseFuse': DenseFuse, 'VIFNet': VIFNet, 'NestFuse': NestFuse, 'RFNNest': RFNNest,
-             'DeepFuse': DeepFuse, 'DBNet': DBNet, 'SEDRFuse': SEDRFuse, 'IFCNN': IFCNN, 'DIFNet': DIFNet, 'PMGI': PMGI, 'UNFusion': UNFusion, 'MAFusion': MAFusion, 'Res2Fusion': Res2Fusion}[args.model]().to(device)
+    model = build_model(args).to(device)   # (--model MyFusion takes --encoder, --decoder, --fusion_method, ...: common.py)
     if is_distributed:
         broadcast_parameters(model, 0)  # replaces the reference's init_weights.pth + DDP constructor broadcast
 
