@@ -174,6 +174,26 @@ int mmif_mixdw_dgrad(const float* gy, const float* w, float* dx, int32_t n, int3
 size_t mmif_mixdw_wgrad_workspace(int32_t n, int32_t c, int32_t nseg, int32_t k0, int32_t h, int32_t wd);
 int mmif_mixdw_wgrad(const float* x, const float* gy, float* dw, float* db, int32_t n, int32_t c, int32_t nseg, int32_t k0, int32_t h,
                      int32_t wd, int32_t reflect, void* workspace, size_t workspace_bytes, void* stream);
+/* hierarchical depth-wise chain (Res2ConvBlock.dwconvs core/block.py:334-340): x, y, gy, dx [n][nseg * c][h][wd] fp32 NCHW.  Segment i =
+ * channels [i c, (i + 1) c); segment 0 is a 1 x 1 depth-wise conv, every later one a 3 x 3 (stride 1, padding 1: reflect without edge repeat, or
+ * zeros, applied to each stage's own input inside the plane), and from the third on a segment convolves the sum of its input and the previous
+ * segment's output.  Legal: 1 <= nseg <= 8, c >= 1, with reflect padding and nseg >= 2 h, wd >= 2, fewer than 2^31 elements; anything else
+ * returns MMIF_EINVAL before any launch (the workspace query returns 0).  w, dw: ONE packed buffer, segment 0 at float offset 0 with layout
+ * [c], segment i >= 1 at c + 9 c (i - 1) with layout [c][3][3]; bias, db: [nseg * c] or NULL.
+ *   fwd    in_0 = x_0, in_1 = x_1, in_i = y_{i-1} + x_i (i >= 2);  y_0 = b_0 + w_0 in_0,  y_i = b_i + sum_{u,v} w_i[u][v] in_i[R(yy + u - 1)][R(xx + v - 1)]
+ *   dgrad  G_{nseg-1} = gy_{nseg-1}, G_i = gy_i + dx_{i+1} (1 <= i <= nseg - 2), G_0 = gy_0;  dx_i = the exact adjoint of stage i on G_i (a pixel
+ *          within 1 of an edge also collects its mirror images)
+ *   wgrad  dw_i[ch][u][v] = sum_{n, pixels} G_i in_i[R(..)], db_i = sum G_i, with G_i and in_i formed from the operands: y is the output of
+ *          mmif_res2dw_fwd for this x, dx the output of mmif_res2dw_dgrad for this gy.  Two stages in a fixed order, no atomics, grids that
+ *          depend on the shape only: bit-identical from run to run.  workspace: mmif_res2dw_wgrad_workspace bytes (MMIF_EWORKSPACE if smaller)
+ * One launch per direction (wgrad: two); nothing allocates or synchronises. */
+int mmif_res2dw_fwd(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c, int32_t nseg, int32_t h, int32_t wd,
+                    int32_t reflect, void* stream);
+int mmif_res2dw_dgrad(const float* gy, const float* w, float* dx, int32_t n, int32_t c, int32_t nseg, int32_t h, int32_t wd, int32_t reflect,
+                      void* stream);
+size_t mmif_res2dw_wgrad_workspace(int32_t n, int32_t c, int32_t nseg, int32_t h, int32_t wd);
+int mmif_res2dw_wgrad(const float* x, const float* y, const float* gy, const float* dx, float* dw, float* db, int32_t n, int32_t c, int32_t nseg,
+                      int32_t h, int32_t wd, int32_t reflect, void* workspace, size_t workspace_bytes, void* stream);
 /* depth-wise patch conv (groups == channels, kernel == stride == s in [2, 16], padding 0; Attention.pool core/block.py:404-412 and
  * TransitionBlock(down_mode='stride') :645-654): x, dx [n][c][h][wd]; y, gy [n][c][h / s][wd / s]; w [c][1][s][s]; h, wd >= s.
  * dgrad writes exactly 0 into the rows and columns beyond floor(h / s) s and floor(wd / s) s.  wgrad runs two stages in a fixed order

@@ -210,6 +210,38 @@ class _MixDwFn(torch.autograd.Function):
         return (dx, None, None, None, *dws, *dbs)
 
 
+class _Res2DwFn(torch.autograd.Function):
+    """hierarchical depth-wise chain on csrc/res2dw.hip: the UN-chunked tensor of nseg * c channels, segment 0 through a 1 x 1 and every later
+    segment through a 3 x 3 depth-wise conv of (its input + the previous segment's output, from the third segment on), the result written in
+    place of the concatenation -- Res2ConvBlock.dwconvs in one launch per direction.  params = the nseg weights [c, 1, k, k], then the nseg
+    biases (all of them or none).  Saved: x, y and the packed weights; the backward runs the input gradient, then the weight gradient on it."""
+
+    @staticmethod
+    def forward(ctx, x, reflect, nseg, *params):
+        T.require_device(x, "ConvLayer input")
+        ws, bs = params[:nseg], params[nseg:]
+        xd = x.detach().contiguous().float()
+        wp = torch.cat([w.detach().reshape(-1) for w in ws]).float() if nseg > 1 else ws[0].detach().reshape(-1).contiguous().float()
+        bp = None
+        if bs:
+            bp = torch.cat([b.detach() for b in bs]).float() if nseg > 1 else bs[0].detach().contiguous().float()
+        y = T.res2dw_fwd(xd, wp, bp, nseg, reflect)
+        ctx.saved = (xd, y, wp)
+        ctx.meta = (reflect, nseg, [tuple(w.shape) for w in ws], bool(bs))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xd, y, wp = ctx.saved
+        reflect, nseg, shapes, has_bias = ctx.meta
+        gy = gy.contiguous().float()
+        dx = T.res2dw_dgrad(gy, wp, nseg, reflect)
+        dwp, dbp = T.res2dw_wgrad(xd, y, gy, dx, nseg, reflect, has_bias)
+        dws = [d.reshape(sh) for d, sh in zip(torch.split(dwp, [sh[0] * sh[2] * sh[3] for sh in shapes]), shapes)]
+        dbs = list(torch.chunk(dbp, nseg)) if has_bias else []
+        return (dx if ctx.needs_input_grad[0] else None, None, None, *dws, *dbs)
+
+
 class _PatchConvFn(torch.autograd.Function):
     """depth-wise nn.Conv2d with kernel == stride in 2..16 and padding 0 (groups == channels) on csrc/conv_general.hip -- Attention.pool,
     TransitionBlock(down_mode='stride')"""
@@ -470,16 +502,20 @@ class MixConvBlock(SepConvBlock):
 class Res2ConvBlock(SepConvBlock):
     """reference core/block.py:286-350 (Res2Fusion): the expanded features are split into `scale` groups of in_ch channels that go
     through depth-wise convs hierarchically -- group i adds the previous group's output (from the third group on) before its own
-    depth-wise conv (1x1 for the first group, 3x3 after) -- and are concatenated again."""
+    depth-wise conv (1x1 for the first group, 3x3 after) -- and are concatenated again.  With scale <= 8 and no norm on the depth-wise layers
+    that chain is ONE launch of csrc/res2dw.hip per direction on the un-chunked tensor (no chunk copies, no adds, no concatenation); otherwise
+    (and on CPU tensors) the layers run one by one (_mix_layers)."""
 
     def __init__(self, in_ch, out_ch, scale=4, bias=False, norm=None, act=nn.ReLU6, residual=True, attention=False):
         super(Res2ConvBlock, self).__init__(in_ch, out_ch, scale=scale, bias=bias, norm=norm, act=act, residual=residual, attention=attention)
         width = in_ch
         self.dwconvs = nn.ModuleList([ConvLayer(width, width, ksize=3 if i > 0 else 1, groups=width, bias=bias, norm=norm, act=None)
                                       for i in range(scale)])
+        self._fused = scale <= 8 and norm is None
 
-    def _mix(self, x):
-        xs = torch.chunk(self.pwconv1(x), self.scale, dim=1)
+    def _mix_layers(self, x):
+        """the reference's per-layer path on an already expanded tensor"""
+        xs = torch.chunk(x, self.scale, dim=1)
         if self.scale == 1:
             return self.dwconvs[0](xs[0])
         outs, y = [], None
@@ -488,6 +524,14 @@ class Res2ConvBlock(SepConvBlock):
             y = self.dwconvs[i](y)
             outs.append(y)
         return concat_fusion(outs)
+
+    def _mix(self, x):
+        x = self.pwconv1(x)
+        if not (self._fused and x.is_cuda):
+            return self._mix_layers(x)
+        convs = [d.layers[0] for d in self.dwconvs]
+        biases = [c.bias for c in convs if c.bias is not None]
+        return _Res2DwFn.apply(x, any(d._geom[2] for d in self.dwconvs), self.scale, *[c.weight for c in convs], *biases)
 
 
 class _SraFn(torch.autograd.Function):

@@ -96,6 +96,10 @@ SIGNATURES = {
     "mmif_mixdw_dgrad": (_i32, [_vp, _vp, _vp] + [_i32] * 7 + [_vp]),
     "mmif_mixdw_wgrad_workspace": (_sz, [_i32] * 6),
     "mmif_mixdw_wgrad": (_i32, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp, _sz, _vp]),
+    "mmif_res2dw_fwd": (_i32, [_vp, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
+    "mmif_res2dw_dgrad": (_i32, [_vp, _vp, _vp] + [_i32] * 6 + [_vp]),
+    "mmif_res2dw_wgrad_workspace": (_sz, [_i32] * 5),
+    "mmif_res2dw_wgrad": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp] + [_i32] * 6 + [_vp, _sz, _vp]),
     "mmif_patchconv_fwd": (_i32, [_vp, _vp, _vp, _vp] + [_i32] * 5 + [_vp]),
     "mmif_patchconv_dgrad": (_i32, [_vp, _vp, _vp] + [_i32] * 5 + [_vp]),
     "mmif_patchconv_wgrad_workspace": (_sz, [_i32, _i32]),

@@ -946,6 +946,46 @@ def mixdw_wgrad(x, gy, nseg, k0, reflect, want_bias):
     return dw, db
 
 
+# ------------------------------------------------------------------ hierarchical depth-wise chain (csrc/res2dw.hip): segment 0 is 1 x 1, the others 3 x 3
+def res2dw_packed_numel(c, nseg):
+    return c + 9 * c * (nseg - 1)
+
+
+def res2dw_fwd(x, w, bias, nseg, reflect):
+    """x [N, nseg * c, H, W]; w: the packed weights (segment 0 at 0 as [c], segment i >= 1 at c + 9 c (i - 1) as [c][3][3]); bias [nseg * c] or None"""
+    _f32c(x, "x"), _f32c(w, "weight")
+    n, ch, h, wd = x.shape
+    c = ch // nseg
+    assert c * nseg == ch and w.numel() == res2dw_packed_numel(c, nseg) and (bias is None or bias.numel() == ch), "res2dw_fwd: operand sizes"
+    y = torch.empty_like(x)
+    check(lib.mmif_res2dw_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), n, c, nseg, h, wd, int(reflect), stream_ptr()), "res2dw_fwd")
+    return y
+
+
+def res2dw_dgrad(gy, w, nseg, reflect):
+    _f32c(gy, "gy"), _f32c(w, "weight")
+    n, ch, h, wd = gy.shape
+    c = ch // nseg
+    assert c * nseg == ch and w.numel() == res2dw_packed_numel(c, nseg), "res2dw_dgrad: operand sizes"
+    dx = torch.empty_like(gy)
+    check(lib.mmif_res2dw_dgrad(_ptr(gy), _ptr(w), _ptr(dx), n, c, nseg, h, wd, int(reflect), stream_ptr()), "res2dw_dgrad")
+    return dx
+
+
+def res2dw_wgrad(x, y, gy, dx, nseg, reflect, want_bias):
+    """y = res2dw_fwd(x, ...), dx = res2dw_dgrad(gy, ...) -> (dw packed like the weights, db [nseg * c] or None)"""
+    _f32c(x, "x"), _f32c(y, "y"), _f32c(gy, "gy"), _f32c(dx, "dx")
+    n, ch, h, wd = x.shape
+    c = ch // nseg
+    assert c * nseg == ch and y.shape == x.shape and gy.shape == x.shape and dx.shape == x.shape, "res2dw_wgrad: operand sizes"
+    dw = torch.empty(res2dw_packed_numel(c, nseg), dtype=torch.float32, device=x.device)
+    db = torch.empty(ch, dtype=torch.float32, device=x.device) if want_bias else None
+    ws = torch.empty(lib.mmif_res2dw_wgrad_workspace(n, c, nseg, h, wd) // 4 + 1, dtype=torch.float32, device=x.device)
+    check(lib.mmif_res2dw_wgrad(_ptr(x), _ptr(y), _ptr(gy), _ptr(dx), _ptr(dw), _ptr(db), n, c, nseg, h, wd, int(reflect), _ptr(ws), ws.numel() * 4,
+                                stream_ptr()), "res2dw_wgrad")
+    return dw, db
+
+
 # ------------------------------------------------------------------ resampling glue on NCHW fp32 (max-pool, nearest up-sampling, reflect pad / crop)
 def maxpool_nchw_fwd(x, k):
     _f32c(x, "x")
