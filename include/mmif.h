@@ -680,6 +680,9 @@ void mmif_debug_set_wgrad_dma_blocks(int32_t blocks);
  * layers): 1 (default) = wgrad_dma_kernel does not stage the channel-block planes of a ragged last group that lie past the
  * tensor (their products are never reduced), 0 = it re-reads the last real plane for them as before.  Identical dW / db either way. */
 void mmif_debug_set_ragged(int32_t mode);
+/* Bias-gradient sums of wgrad_dma_kernel: 1 (default) = only the blocks of input-channel group 0 compute them (the reduce reads db from
+ * those blocks alone), 0 = every block does, as before.  Identical dW / db and sign bytes either way (tests/test_gpu_wgrad_bias.py). */
+void mmif_debug_set_wgrad_bias(int32_t mode);
 /* Deferred weight-gradient reductions (round 5, csrc/reduce_defer.hip).  Every weight-gradient entry point above ends in a small fixed-order
  * reduce launch over its per-block partial sums -- autograd's accumulation of `convolution_backward`'s weight / bias gradients into `.grad`
  * (`train.py:71`).  Between begin() and flush() the reduces of mmif_conv2d_reflect_bwd_wide, mmif_conv2d_reflect_bwd_pair and

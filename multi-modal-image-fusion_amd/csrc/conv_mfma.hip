@@ -1655,7 +1655,7 @@ constexpr int WDL_ITERS = (WD_PIECES + D_LOAD - 1) / D_LOAD;   // 19 pieces per 
 
 __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV tx, TV tg, float* __restrict__ partial, int tiles_x,
                                                                                int tpi, int total, int G, int n_icg, int n_ocg, SignMap sgn,
-                                                                               int ragged_skip) {
+                                                                               int ragged_skip, int bias_all) {
     constexpr int TP = MT + 2;
     __shared__ __attribute__((aligned(16))) char s_buf[2 * WD_BUF_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1794,9 +1794,14 @@ __global__ __launch_bounds__((D_CONS + D_LOAD) * 64, 3) void wgrad_dma_kernel(TV
     }
     const uint4 ones_u = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
     const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_u);
-    // The bias sums are the waves' with icf == 0: a scalar, and the tile loop specialised on it -- two copies of the loop, chosen once,
-    // each k-step one basic block (tested per k-step it cut the unrolled tile into 17 blocks).
-    const bool bias_role = __builtin_amdgcn_readfirstlane(icf == 0) != 0;
+    // The bias sums are the waves' with icf == 0, in the blocks of input group 0: the only ones the reduce reads (grouped_wgrad_map::slot;
+    // tools/check_wgrad_maps.cpp walks the maps for it), so the other blocks neither compute nor store them (bias_all = the debug
+    // placement mmif_debug_set_wgrad_bias(0): every block does, as before).  A scalar, and the tile loop specialised on it -- two
+    // copies of the loop, chosen once, each k-step one basic block (tested per k-step it cut the unrolled tile into 17 blocks).
+    // (Measured and not kept: the four LOADER waves owning the sums of those blocks, one fragment each -- 8 MFMAs per tile on every SIMD
+    // instead of 32 on SIMD 0, but 16 more transposing reads per loader and tile, where the consumers' chain re-uses fragments it
+    // holds: decode.0's launch 422.1 -> 419.8 us, decode.1's 243.4 -> 247.8 us)
+    const bool bias_role = (icg == 0 || bias_all != 0) && __builtin_amdgcn_readfirstlane(icf == 0) != 0;
     auto tile_loop = [&](auto bias_c) {
     constexpr bool BIAS = decltype(bias_c)::value != 0;
     // (lane coordinates derived inside each copy, behind an asm the compiler cannot hoist: shared by the two copies they stayed live
@@ -2576,7 +2581,7 @@ static int launch_wgrad_dma(const WgradRoute& r, const TV& tx, const TV& tg, flo
                             hipStream_t st, SignMap sgn = SignMap{nullptr, 0, 0, 0}) {
     ws = defer_ws(ws, (size_t)r.G * r.n_icg * r.n_ocg * WD_PER * sizeof(float));      // (csrc/wgrad_reduce.hpp: an arena slot while reductions are deferred)
     hipLaunchKernelGGL(wgrad_dma_kernel, dim3(r.G * r.n_icg * r.n_ocg), dim3((D_CONS + D_LOAD) * 64), 0, st, tx, tg, ws, r.tiles_x, r.tpi, r.total, r.G,
-                       r.n_icg, r.n_ocg, sgn, g_conv_switches.wgrad_ragged);
+                       r.n_icg, r.n_ocg, sgn, g_conv_switches.wgrad_ragged, g_conv_switches.wgrad_bias == 0 ? 1 : 0);
     if (int rc = check_launch("wgrad_dma")) return rc;
     return wgrad_reduce_launch(wgrad_dma_reduce{{dw, db, cin, cout, r.n_icg, r.n_ocg}}, ws, r.G, accumulate, st);
 }
@@ -2640,6 +2645,7 @@ extern "C" void mmif_debug_set_conv1x1_stream(int32_t mode) { g_conv_switches.co
 extern "C" void mmif_debug_set_bwd_pair_dma(int32_t mode) { g_conv_switches.bwd_pair_dma = mode ? 1 : 0; }
 extern "C" void mmif_debug_set_thin_wide(int32_t mode) { g_conv_switches.thin_wide = mode ? 1 : 0; }
 extern "C" void mmif_debug_set_ragged(int32_t mode) { g_conv_switches.wgrad_ragged = mode ? 1 : 0; }
+extern "C" void mmif_debug_set_wgrad_bias(int32_t mode) { g_conv_switches.wgrad_bias = mode ? 1 : 0; }
 extern "C" void mmif_debug_set_wgrad_dma_blocks(int32_t blocks) { g_conv_switches.wgrad_dma_blocks = blocks < 8 ? 8 : (blocks > 256 ? 256 : blocks); }
 
 extern "C" size_t mmif_packed_weight_bytes(int32_t cout, int32_t cin, int32_t ksize) {

@@ -52,6 +52,8 @@ struct ConvSwitches {
     int wgrad_dma_blocks = 256;   // mmif_debug_set_wgrad_dma_blocks: persistent blocks of wgrad_dma_kernel (one per CU); fewer leave CUs to a
                                   // kernel running concurrently on another stream (the intra-step overlap experiment)
     int wgrad_ragged = 1;         // mmif_debug_set_ragged(0): wgrad_dma_kernel stages the padded planes of a ragged channel group too
+    int wgrad_bias = 1;           // mmif_debug_set_wgrad_bias(0): every block of wgrad_dma_kernel sums the bias gradient, not only those of input
+                                  // group 0 that the reduce reads
     int bwd_pair_dma = 1;         // mmif_debug_set_bwd_pair_dma(0): the register-staged bwd_pair_kernel
     int wgrad_taprow = 1;         // $MMIF_WGRAD_TAPROW=0: keep the per-input-group kernel (A/B timing)
 };

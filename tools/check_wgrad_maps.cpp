@@ -4,7 +4,8 @@
 // tests/wgrad_bits_cases.py plus the ragged ones each layout allows, walk idx over the launcher's grid (cdiv(n, 64) * 64) and require:
 //   - every dW / db element is produced exactly once, and db not at all when it is null;
 //   - every off is in [0, stride);
-//   - no two outputs share an off.
+//   - no two outputs share an off;
+//   - wgrad_dma_reduce (the single and the deferred launch run the same map): db is read from the blocks of input group 0 only.
 #include <stdio.h>
 
 #include <vector>
@@ -66,6 +67,28 @@ static void check_conv(const char* name, int cin, int cout, int kk, Make make) {
 }
 static int cdiv_(int a, int b) { return (a + b - 1) / b; }
 
+// The grouped maps read the bias sums from the blocks of input group 0 alone, so the blocks of the other groups need not write theirs
+// (wgrad_dma_kernel and wgrad_mfma_kernel compute none there): no idx of the walk may read a bias slot of a group icg > 0.
+template <class Map>
+static void check_bias_slots(const char* name, const Map& m, int bias_off) {   // bias_off: where the bias sums start in a block partial
+    ++g_cases;
+    int bad = 0, from_group0 = 0;
+    const long long walk = (long long)((m.n() + 63) / 64) * 64;
+    for (long long idx = 0; idx < walk; ++idx) {
+        const RedSlot s = m.slot((int)idx);
+        if (s.off < 0) continue;
+        const long long grp = s.off / Map::PER, e = s.off % Map::PER;
+        if (e < bias_off) continue;
+        // (group = icg + n_icg * ocg or icg * n_ocg + ocg: recover icg by asking the map)
+        bool is_group0 = false;
+        for (int ocg = 0; ocg < m.n_ocg; ++ocg) is_group0 |= grp == m.group(0, ocg);
+        if (is_group0) ++from_group0;
+        else if (bad++ < 5) printf("  %s: idx %lld reads bias slot %lld of block group %lld, an input group > 0\n", name, idx, e - bias_off, grp);
+    }
+    if (from_group0 != m.cout && bad++ < 5) printf("  %s: %d bias sums read from input group 0, %d output channels\n", name, from_group0, m.cout);
+    if (bad) { ++g_failed; printf("FAIL %s: bias slots (%d findings)\n", name, bad); }
+}
+
 template <int KS, int MFW, int ICF>
 static void check_mfma(int cin, int cout) {
     using M = wgrad_mfma_reduce<KS, MFW, ICF>;
@@ -82,9 +105,17 @@ static void check_image(int c) {
 int main() {
     // wgrad_dma: multiples of 8, ragged last groups included
     const int dma[][2] = {{64, 64}, {128, 64}, {64, 128}, {192, 128}, {64, 136}, {136, 64}, {120, 56}, {8, 8}, {200, 72}};
-    for (auto& c : dma)
+    for (auto& c : dma) {
         check_conv<wgrad_dma_reduce>("wgrad_dma_reduce", c[0], c[1], 9,
                                      [&](float* dw, float* db) { return wgrad_dma_reduce{{dw, db, c[0], c[1], cdiv_(c[0], 64), cdiv_(c[1], 64)}}; });
+        // (the deferred launch of csrc/reduce_defer.hip runs this same map: one answer for both)
+        std::vector<float> dw((size_t)c[1] * c[0] * 9);
+        check_bias_slots("wgrad_dma_reduce", wgrad_dma_reduce{{dw.data(), nullptr, c[0], c[1], cdiv_(c[0], 64), cdiv_(c[1], 64)}}, 64 * 64 * 9);
+    }
+    {   // NestFuse's widest layer: five input groups
+        std::vector<float> dw((size_t)152 * 304 * 9);
+        check_bias_slots("wgrad_dma_reduce 304 -> 152", wgrad_dma_reduce{{dw.data(), nullptr, 304, 152, 5, 3}}, 64 * 64 * 9);
+    }
     // wgrad_mfma: every instantiation the library launches; any channel count
     const int any[][2] = {{16, 16}, {8, 8}, {24, 40}, {48, 16}, {33, 7}, {64, 32}, {100, 70}, {1, 1}};
     for (auto& c : any) {
