@@ -382,6 +382,29 @@ int mmif_nonlocal_spatial_fwd(const float* x, float* y, float* l, void* scal, in
 int mmif_nonlocal_spatial_bwd(const float* x, const float* y, const float* l, const void* scal, const float* g, float* dx, int32_t n, int32_t c,
                               int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Res2Fusion's non-local channel attention, channel_pooling(x, 'nl') of core/fusion.py:137-150.  x, y, g, dx: plain NCHW fp32 [n][c][h][w];
+ * e, attn: fp32 [n][c][c], the energy X X^T (symmetric bit for bit) and its row softmax after the min-max normalisation over the whole batch;
+ * scal: 16 words in the layout of the spatial kernels (lo, hi, 1 / (hi - lo), pad, then the positions of the minimum and of the maximum as
+ * (sample, row, column, pad); ties go to the first element in C order of [n][c][c]).  fwd writes y, e, attn and scal; bwd reads them.
+ * Limits: 1 <= n <= 65535, 1 <= c <= 256, n * c >= 2, h, w >= 1, h * w < 2^30; anything else returns MMIF_EINVAL (the workspace query returns
+ * 0).  A constant energy tensor (hi == lo) is NaN, as in the reference.  The workspace is scratch: bwd does not need what fwd left in it.
+ * Results are bit-identical from run to run (no atomics). */
+size_t mmif_nonlocal_channel_workspace(int32_t n, int32_t c, int32_t h, int32_t w);
+int mmif_nonlocal_channel_fwd(const float* x, float* y, float* e, float* attn, void* scal, int32_t n, int32_t c, int32_t h, int32_t w,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mmif_nonlocal_channel_bwd(const float* x, const float* e, const float* attn, const void* scal, const float* g, float* dx, int32_t n,
+                              int32_t c, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The join of attention_fusion (core/fusion.py:42-59) once its pooled maps exist, element-wise over `count` fp32 words:
+ *   wf(a, b) = w t1 + (1 - w) t2,  w = a / max(a + b, 1e-7f);  fs = wf(s1, s2),  fc = wf(c1, c2);
+ *   mode 0 'sa' fs, 1 'ca' fc, 2 'sca' (fs + fc) / 2, 3 'wavg' w' fs + (1 - w') fc with w' = fs / max(fs + fc, 1e-7f).
+ * The maps a mode does not use, and their gradients, must be NULL (MMIF_EINVAL otherwise).  bwd writes all gradients of the mode in one
+ * launch from the forward operands alone; the clamp passes gradient to a + b where a + b >= 1e-7f (equality included), as torch does. */
+int mmif_fuse_join_fwd(const float* t1, const float* t2, const float* s1, const float* s2, const float* c1, const float* c2, float* out,
+                       int32_t mode, size_t count, void* stream);
+int mmif_fuse_join_bwd(const float* t1, const float* t2, const float* s1, const float* s2, const float* c1, const float* c2, const float* g,
+                       float* dt1, float* dt2, float* ds1, float* ds2, float* dc1, float* dc2, int32_t mode, size_t count, void* stream);
+
 /* Multi-head spatial-reduction self-attention core (Attention.forward of core/block.py:416-431) without the [B, heads, N, M] energy
  * tensor.  q, o, go, dq: plain NCHW fp32 planes [b][heads * d][n]; k, v, dk, dv: [b][heads * d][m]; head h owns channels h d ... (h + 1) d - 1;
  *   o[b][h d + c][i] = sum_j softmax_j(scale sum_c' q[b][h d + c'][i] k[b][h d + c'][j]) v[b][h d + c][j],

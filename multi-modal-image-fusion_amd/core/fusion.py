@@ -4,9 +4,11 @@
 element_fusion runs on the HIP element-fusion kernels (mmif_fuse_elem_{fwd,bwd}); inside the models
 concat_fusion is zero-copy (channel-block views) and DenseFuse's 'sum' runs on blocked buffers.
 attention_fusion 'sa' / 'ca' / 'sca' with the reference's default pooling (spatial 'l1', channel 'avg') runs on
-the HIP attention kernels (mmif_fuse_attn_{fwd,bwd}); spatial 'nl' pooling (Res2Fusion) runs on the streaming non-local kernels
-(mmif_nonlocal_spatial_{fwd,bwd}, no [B, H*W, H*W/64] energy tensor); the remaining pooling modes are tensor-level compositions kept for
-API completeness.
+the HIP attention kernels (mmif_fuse_attn_{fwd,bwd}).  With both poolings 'nl' (Res2Fusion) the whole layer is HIP: the spatial maps on the
+streaming non-local kernels (mmif_nonlocal_spatial_{fwd,bwd}, no [B, H*W, H*W/64] energy tensor), the channel maps on
+mmif_nonlocal_channel_{fwd,bwd} and the join of the four maps (both weighted_fusion calls, the clamp, the mean) on one launch per direction
+(mmif_fuse_join_{fwd,bwd}); $MMIF_NONLOCAL=torch keeps the tensor-level composition for all of it as the cross-check.  The remaining pooling
+modes are tensor-level compositions kept for API completeness.
 """
 import os
 
@@ -86,6 +88,42 @@ class _NonlocalSpatialFn(torch.autograd.Function):
         return T.nonlocal_spatial_bwd(x, y, l, scal, g.contiguous())
 
 
+class _NonlocalChannelFn(torch.autograd.Function):
+    """channel_pooling(x, 'nl') on csrc/nonlocal_channel.hip; saved for backward are x, the energy and the attention matrix [B, C, C] and
+    the 16-word scalar block (global min / max of the energy and where they sit)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.detach().contiguous()
+        y, e, attn, scal = T.nonlocal_channel_fwd(x)
+        ctx.save_for_backward(x, e, attn, scal)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, e, attn, scal = ctx.saved_tensors
+        return T.nonlocal_channel_bwd(x, e, attn, scal, g.contiguous())
+
+
+class _FusionJoinFn(torch.autograd.Function):
+    """attention_fusion's join of the two features with their pooled maps (s1, s2 spatial, c1, c2 channel; the pair a mode does not use is
+    None): one launch per direction, nothing saved but the operands, which the 'nl' functions keep anyway."""
+
+    @staticmethod
+    def forward(ctx, t1, t2, s1, s2, c1, c2, mode):
+        ops = tuple(t.detach().contiguous() if t is not None else None for t in (t1, t2, s1, s2, c1, c2))
+        ctx.save_for_backward(*(t for t in ops if t is not None))
+        ctx.have = tuple(t is not None for t in ops)
+        ctx.mode = mode
+        return T.fuse_join_fwd(*ops, mode)
+
+    @staticmethod
+    def backward(ctx, g):
+        it = iter(ctx.saved_tensors)
+        ops = tuple(next(it) if h else None for h in ctx.have)
+        return (*T.fuse_join_bwd(*ops, g.contiguous(), ctx.mode), None)
+
+
 def _nonlocal_impl():
     """$MMIF_NONLOCAL = hip (default) | torch: the streaming kernels, or the tensor-level composition everywhere (cross-check)"""
     v = os.environ.get("MMIF_NONLOCAL", "hip")
@@ -114,9 +152,8 @@ def concat_fusion(tensors, dim=1):
 
 def _nonlocal(t, spatial):
     """Res2Fusion's non-local attention maps (reference core/fusion.py:96-113 spatial, :137-150 channel): softmax over a min-max
-    normalised energy, applied to the features, plus the identity.  Tensor-level composition (two batched matmuls): the channel form
-    (energy [B, C, C]) always, the spatial form only where the streaming kernels do not apply (CPU, H or W < 8, C > 256) or under
-    $MMIF_NONLOCAL=torch."""
+    normalised energy, applied to the features, plus the identity.  Tensor-level composition (two batched matmuls), used only where the
+    kernels do not apply (CPU, C > 256; spatial: H or W < 8; channel: B * C < 2) or under $MMIF_NONLOCAL=torch."""
     b, c, h, w = t.shape
     flat = t.reshape(b, c, -1)
     if spatial:   # queries: every pixel; keys / values: the 8x8 average-pooled map
@@ -154,6 +191,8 @@ def channel_pooling(tensor, mode='avg'):
     if mode == 'max':
         return tensor.amax(dim=(2, 3), keepdim=True)
     if mode == 'nl':
+        if _nonlocal_impl() == 'hip' and T.nonlocal_channel_supported(tensor):
+            return _NonlocalChannelFn.apply(tensor)
         return _nonlocal(tensor, spatial=False)
     if mode == 'nuclear':
         from ._stock import nuclear_pooling
@@ -181,6 +220,14 @@ def attention_fusion(tensor1, tensor2, mode='sca', spatial_mode='l1', channel_mo
     if (tensor1.is_cuda and mode in T.ATTN_MODES and spatial_mode == 'l1' and channel_mode == 'avg' and tensor1.dim() == 4
             and tensor1.shape == tensor2.shape):
         return _AttnFusionFn.apply(tensor1, tensor2, T.ATTN_MODES[mode])
+    if (spatial_mode == 'nl' and channel_mode == 'nl' and _nonlocal_impl() == 'hip' and tensor1.is_cuda and tensor2.is_cuda
+            and tensor1.dtype == tensor2.dtype == torch.float32 and tensor1.dim() == 4 and tensor1.shape == tensor2.shape):
+        s1 = s2 = c1 = c2 = None
+        if mode != 'ca':
+            s1, s2 = spatial_pooling(tensor1, 'nl'), spatial_pooling(tensor2, 'nl')
+        if mode != 'sa':
+            c1, c2 = channel_pooling(tensor1, 'nl'), channel_pooling(tensor2, 'nl')
+        return _FusionJoinFn.apply(tensor1, tensor2, s1, s2, c1, c2, T.JOIN_MODES[mode])
     f_spatial = spatial_fusion(tensor1, tensor2, spatial_mode, softmax=False)
     f_channel = channel_fusion(tensor1, tensor2, channel_mode, softmax=False)
     if mode == 'sa':

@@ -143,8 +143,8 @@ class UNFusion(_FusionModel):
 class Res2Fusion(_FusionModel):
     '''Res2Fusion (reference core/model.py:439-470): a dense encoder of Res2ConvBlocks (point-wise + hierarchical depth-wise convs,
     ReLU6) and double non-local attention fusion.  Convs, depth-wise convs and activations on the HIP kernels; the spatial non-local
-    attention map runs on the streaming kernels of csrc/nonlocal.hip (no [B, H*W, H*W/64] energy tensor, so the 1224 x 1024 frame fits);
-    the channel map (energy [B, C, C]) is a tensor-level composition (two small batched matmuls).'''
+    attention map runs on the streaming kernels of csrc/nonlocal.hip (no [B, H*W, H*W/64] energy tensor, so the 1224 x 1024 frame fits),
+    the channel map (energy [B, C, C]) and the join of the four maps on those of csrc/nonlocal_channel.hip.'''
 
     def __init__(self):
         super(Res2Fusion, self).__init__()

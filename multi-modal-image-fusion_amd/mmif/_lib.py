@@ -171,6 +171,11 @@ SIGNATURES = {
     "mmif_nonlocal_spatial_workspace": (_sz, [_i32] * 4),
     "mmif_nonlocal_spatial_fwd": (_i32, [_vp] * 4 + [_i32] * 4 + [_vp, _sz, _vp]),
     "mmif_nonlocal_spatial_bwd": (_i32, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
+    "mmif_nonlocal_channel_workspace": (_sz, [_i32] * 4),
+    "mmif_nonlocal_channel_fwd": (_i32, [_vp] * 5 + [_i32] * 4 + [_vp, _sz, _vp]),
+    "mmif_nonlocal_channel_bwd": (_i32, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
+    "mmif_fuse_join_fwd": (_i32, [_vp] * 7 + [_i32, _sz, _vp]),
+    "mmif_fuse_join_bwd": (_i32, [_vp] * 13 + [_i32, _sz, _vp]),
     "mmif_sra_workspace": (_sz, [_i32, _i32, _i32, _i64, _i64]),
     "mmif_sra_fwd": (_i32, [_vp] * 5 + [_i32, _i32, _i32, _i64, _i64, _f32, _vp]),
     "mmif_sra_bwd": (_i32, [_vp] * 9 + [_i32, _i32, _i32, _i64, _i64, _f32, _vp, _sz, _vp]),

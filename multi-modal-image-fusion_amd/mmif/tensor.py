@@ -536,6 +536,70 @@ def nonlocal_spatial_bwd(x, y, l, scal, g):
     return dx
 
 
+# ------------------------------------------------------------------ non-local channel attention and the fusion join (csrc/nonlocal_channel.hip)
+def nonlocal_channel_supported(x):
+    """CUDA fp32 [B,C,H,W] inside the kernels' limits (include/mmif.h); everything else stays on the tensor-level composition"""
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and 1 <= x.shape[0] <= 65535 and 1 <= x.shape[1] <= NONLOCAL_MAX_C
+            and x.shape[0] * x.shape[1] >= 2 and x.shape[2] >= 1 and x.shape[3] >= 1 and x.shape[2] * x.shape[3] < (1 << 30))
+
+
+def nonlocal_channel_workspace(x):
+    n, c, h, w = x.shape
+    nbytes = lib.mmif_nonlocal_channel_workspace(n, c, h, w)
+    if nbytes == 0:
+        raise _lib.MmifError(f"nonlocal_channel_workspace: {lib.mmif_last_error().decode()}")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+
+
+def nonlocal_channel_fwd(x):
+    """y = softmax_rows(minmax-normalised X X^T) X + x; returns (y, e, attn, scal): the energy and the attention matrix [B, C, C] and the
+    scalar block, which the backward pass needs"""
+    _f32c(x, "x")
+    n, c, h, w = x.shape
+    y = torch.empty_like(x)
+    e = torch.empty((n, c, c), dtype=torch.float32, device=x.device)
+    attn = torch.empty_like(e)
+    scal = torch.empty(NONLOCAL_SCALARS, dtype=torch.float32, device=x.device)
+    ws = nonlocal_channel_workspace(x)
+    check(lib.mmif_nonlocal_channel_fwd(_ptr(x), _ptr(y), _ptr(e), _ptr(attn), _ptr(scal), n, c, h, w, _ptr(ws), ws.numel() * 4, stream_ptr()),
+          "nonlocal_channel_fwd")
+    return y, e, attn, scal
+
+
+def nonlocal_channel_bwd(x, e, attn, scal, g):
+    _f32c(x, "x"), _f32c(e, "e"), _f32c(attn, "attn"), _f32c(scal, "scal"), _f32c(g, "g")
+    n, c, h, w = x.shape
+    dx = torch.empty_like(x)
+    ws = nonlocal_channel_workspace(x)
+    check(lib.mmif_nonlocal_channel_bwd(_ptr(x), _ptr(e), _ptr(attn), _ptr(scal), _ptr(g), _ptr(dx), n, c, h, w, _ptr(ws), ws.numel() * 4,
+                                        stream_ptr()), "nonlocal_channel_bwd")
+    return dx
+
+
+JOIN_MODES = {"sa": 0, "ca": 1, "sca": 2, "wavg": 3}
+
+
+def fuse_join_fwd(t1, t2, s1, s2, c1, c2, mode):
+    """attention_fusion's join of the pooled maps (full-size fp32 tensors; the pair a mode does not use is None)"""
+    for name, t in (("t1", t1), ("t2", t2), ("s1", s1), ("s2", s2), ("c1", c1), ("c2", c2)):
+        if t is not None:
+            _f32c(t, name)
+    out = torch.empty_like(t1)
+    check(lib.mmif_fuse_join_fwd(_ptr(t1), _ptr(t2), _ptr(s1), _ptr(s2), _ptr(c1), _ptr(c2), _ptr(out), mode, t1.numel(), stream_ptr()),
+          "fuse_join_fwd")
+    return out
+
+
+def fuse_join_bwd(t1, t2, s1, s2, c1, c2, g, mode):
+    """returns (dt1, dt2, ds1, ds2, dc1, dc2), None where the mode has no such map"""
+    _f32c(g, "g")
+    new = lambda t: torch.empty_like(t1) if t is not None else None
+    d = [torch.empty_like(t1), torch.empty_like(t1), new(s1), new(s2), new(c1), new(c2)]
+    check(lib.mmif_fuse_join_bwd(_ptr(t1), _ptr(t2), _ptr(s1), _ptr(s2), _ptr(c1), _ptr(c2), _ptr(g), *(_ptr(t) for t in d), mode, t1.numel(),
+                                 stream_ptr()), "fuse_join_bwd")
+    return tuple(d)
+
+
 # ------------------------------------------------------------------ spatial-reduction self-attention core (plain NCHW fp32; csrc/attention.hip)
 SRA_MAX_A = 256
 SRA_HEAD_DIMS = (8, 16, 32)
