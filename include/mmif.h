@@ -405,6 +405,28 @@ int mmif_fuse_join_fwd(const float* t1, const float* t2, const float* s1, const 
 int mmif_fuse_join_bwd(const float* t1, const float* t2, const float* s1, const float* s2, const float* c1, const float* c2, const float* g,
                        float* dt1, float* dt2, float* ds1, float* ds2, float* dc1, float* dc2, int32_t mode, size_t count, void* stream);
 
+/* attention_fusion (core/fusion.py:42-81) for every tensor-level pooling mode in two passes per direction (csrc/attn_fuse.hip).  t1, t2, out, g,
+ * dt1, dt2: plain NCHW fp32 [n][c][h][w].
+ *   spatial_mode  pool over the channels, s1, s2 fp32 [n][h*w]:  0 'sum', 1 'mean', 2 'l1', 3 'l2', 4 'linf',
+ *                 5 sum_c softmax_c(|x|) |x| (SEDRFuse's activity; gradient p_c (1 + |x_c| - s) sign(x_c))
+ *   channel_mode  pool over the plane, c1, c2 fp32 [n][c]:  0 'avg', 1 'max', which also writes the row-major position of the maximum,
+ *                 ci1, ci2 int32 [n][c]
+ *   mode          0 'sa', 1 'ca', 2 'sca', 3 'wavg': the join of mmif_fuse_join_* above, same arithmetic and clamp rule
+ * fwd writes out and the pools; bwd reads the pools and writes dt1, dt2.  The pools a mode does not use, and ci1, ci2 unless the mode uses
+ * channel_mode 1, must be NULL (MMIF_EINVAL otherwise); both mode arguments must be in range even where the mode does not use them.
+ * Sub-gradients follow torch's CPU autograd on the reference's ops: 'l1' sign(x) with sign(0) = 0; 'l2' x / |x|_2 and 0 for a zero vector;
+ * 'linf' all to the FIRST channel holding the maximum; 'max' (max_pool2d over the plane) all to the FIRST position in row-major order, element 0
+ * of a constant plane.  Limits: 1 <= n, c <= 65535, h, w >= 1, h * w < 2^30; anything else returns MMIF_EINVAL before any launch (the workspace
+ * query returns 0); a short workspace returns MMIF_EWORKSPACE.  The workspace is scratch: bwd needs nothing fwd left in it.  No atomics: results
+ * are bit-identical from run to run, and a sample's results do not depend on the batch it sits in.  NaN inputs are out of scope. */
+size_t mmif_attn_fuse_workspace(int32_t n, int32_t c, int32_t h, int32_t w, int32_t mode, int32_t spatial_mode, int32_t channel_mode);
+int mmif_attn_fuse_fwd(const float* t1, const float* t2, float* out, float* s1, float* s2, float* c1, float* c2, int32_t* ci1, int32_t* ci2,
+                       int32_t n, int32_t c, int32_t h, int32_t w, int32_t mode, int32_t spatial_mode, int32_t channel_mode, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int mmif_attn_fuse_bwd(const float* t1, const float* t2, const float* s1, const float* s2, const float* c1, const float* c2, const int32_t* ci1,
+                       const int32_t* ci2, const float* g, float* dt1, float* dt2, int32_t n, int32_t c, int32_t h, int32_t w, int32_t mode,
+                       int32_t spatial_mode, int32_t channel_mode, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Multi-head spatial-reduction self-attention core (Attention.forward of core/block.py:416-431) without the [B, heads, N, M] energy
  * tensor.  q, o, go, dq: plain NCHW fp32 planes [b][heads * d][n]; k, v, dk, dv: [b][heads * d][m]; head h owns channels h d ... (h + 1) d - 1;
  *   o[b][h d + c][i] = sum_j softmax_j(scale sum_c' q[b][h d + c'][i] k[b][h d + c'][j]) v[b][h d + c][j],

@@ -7,8 +7,14 @@ attention_fusion 'sa' / 'ca' / 'sca' with the reference's default pooling (spati
 the HIP attention kernels (mmif_fuse_attn_{fwd,bwd}).  With both poolings 'nl' (Res2Fusion) the whole layer is HIP: the spatial maps on the
 streaming non-local kernels (mmif_nonlocal_spatial_{fwd,bwd}, no [B, H*W, H*W/64] energy tensor), the channel maps on
 mmif_nonlocal_channel_{fwd,bwd} and the join of the four maps (both weighted_fusion calls, the clamp, the mean) on one launch per direction
-(mmif_fuse_join_{fwd,bwd}); $MMIF_NONLOCAL=torch keeps the tensor-level composition for all of it as the cross-check.  The remaining pooling
-modes are tensor-level compositions kept for API completeness.
+(mmif_fuse_join_{fwd,bwd}); $MMIF_NONLOCAL=torch keeps the tensor-level composition for all of it as the cross-check.
+Every other combination of the tensor-level poolings (spatial 'sum' / 'mean' / 'l1' / 'l2' / 'linf', channel 'avg' / 'max') in any of the four
+modes -- 'wavg', UNFusion's default, among them -- and spatial_fusion / channel_fusion with softmax=False run on the fused kernels of
+csrc/attn_fuse.hip (mmif_attn_fuse_{fwd,bwd}: a pooling pass and a join pass forward, a reduction pass and a gradient pass backward, on plain NCHW
+fp32), as does SEDRFuse's strategy (softmax_l1_fusion).  $MMIF_ATTN_FUSE=torch keeps the tensor-level composition as the cross-check; the
+composition also serves CPU tensors, other dtypes, 'nuclear', softmax=True and mixes of 'nl' with another mode.  One deliberate difference: the
+composition's channel 'max' is amax, which splits the gradient of a tied maximum evenly; the kernels follow the reference's max_pool2d and give
+it to the first position in row-major order.
 """
 import os
 
@@ -124,12 +130,52 @@ class _FusionJoinFn(torch.autograd.Function):
         return (*T.fuse_join_bwd(*ops, g.contiguous(), ctx.mode), None)
 
 
+class _AttnFuseFn(torch.autograd.Function):
+    """attention_fusion on csrc/attn_fuse.hip (codes: T.JOIN_MODES, T.AF_SPATIAL, T.AF_CHANNEL); saved for backward are the operands and the
+    pools of the mode: s1, s2 [B, H*W], c1, c2 [B, C] and, for channel 'max', the positions of the maxima."""
+
+    @staticmethod
+    def forward(ctx, t1, t2, mode, spatial_mode, channel_mode):
+        t1, t2 = t1.detach().contiguous(), t2.detach().contiguous()
+        out, pools = T.attn_fuse_fwd(t1, t2, mode, spatial_mode, channel_mode)
+        ctx.save_for_backward(t1, t2, *(t for t in pools if t is not None))
+        ctx.have = tuple(t is not None for t in pools)
+        ctx.codes = (mode, spatial_mode, channel_mode)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        t1, t2, *rest = ctx.saved_tensors
+        it = iter(rest)
+        pools = tuple(next(it) if h else None for h in ctx.have)
+        return (*T.attn_fuse_bwd(t1, t2, pools, g.contiguous(), *ctx.codes), None, None, None)
+
+
 def _nonlocal_impl():
     """$MMIF_NONLOCAL = hip (default) | torch: the streaming kernels, or the tensor-level composition everywhere (cross-check)"""
     v = os.environ.get("MMIF_NONLOCAL", "hip")
     if v not in ("hip", "torch"):
         raise ValueError(f"MMIF_NONLOCAL must be 'hip' or 'torch', got {v!r}")
     return v
+
+
+_SPATIAL_NAMES = ('sum', 'mean', 'l1', 'l2', 'linf', 'nl')
+_CHANNEL_NAMES = ('avg', 'max', 'nuclear', 'nl')
+
+
+def _attn_fuse_impl():
+    """$MMIF_ATTN_FUSE = hip (default) | torch: the fused kernels of csrc/attn_fuse.hip, or the tensor-level composition everywhere (cross-check)"""
+    v = os.environ.get("MMIF_ATTN_FUSE", "hip")
+    if v not in ("hip", "torch"):
+        raise ValueError(f"MMIF_ATTN_FUSE must be 'hip' or 'torch', got {v!r}")
+    return v
+
+
+def _attn_fuse(tensor1, tensor2, mode, spatial_code, channel_code):
+    """the fused route if it applies, else None"""
+    if spatial_code is None or channel_code is None or _attn_fuse_impl() != 'hip' or not T.attn_fuse_supported(tensor1, tensor2):
+        return None
+    return _AttnFuseFn.apply(tensor1, tensor2, T.JOIN_MODES[mode], spatial_code, channel_code)
 
 
 def element_fusion(tensor1, tensor2, mode='sum'):
@@ -201,6 +247,10 @@ def channel_pooling(tensor, mode='avg'):
 
 
 def spatial_fusion(tensor1, tensor2, mode='l1', softmax=True):
+    if not softmax:
+        fused = _attn_fuse(tensor1, tensor2, 'sa', T.AF_SPATIAL.get(mode), 0)
+        if fused is not None:
+            return fused
     s1, s2 = spatial_pooling(tensor1, mode), spatial_pooling(tensor2, mode)
     if softmax:
         s1, s2 = torch.exp(s1), torch.exp(s2)
@@ -208,6 +258,10 @@ def spatial_fusion(tensor1, tensor2, mode='l1', softmax=True):
 
 
 def channel_fusion(tensor1, tensor2, mode='avg', softmax=True):
+    if not softmax:
+        fused = _attn_fuse(tensor1, tensor2, 'ca', 0, T.AF_CHANNEL.get(mode))
+        if fused is not None:
+            return fused
     c1, c2 = channel_pooling(tensor1, mode), channel_pooling(tensor2, mode)
     if softmax:
         c1, c2 = torch.exp(c1), torch.exp(c2)
@@ -228,6 +282,12 @@ def attention_fusion(tensor1, tensor2, mode='sca', spatial_mode='l1', channel_mo
         if mode != 'sa':
             c1, c2 = channel_pooling(tensor1, 'nl'), channel_pooling(tensor2, 'nl')
         return _FusionJoinFn.apply(tensor1, tensor2, s1, s2, c1, c2, T.JOIN_MODES[mode])
+    # a pooling the mode does not use only has to be a valid name (the composition below would evaluate it and throw the result away)
+    sp_code = T.AF_SPATIAL.get(spatial_mode) if mode != 'ca' else (0 if spatial_mode in _SPATIAL_NAMES else None)
+    ch_code = T.AF_CHANNEL.get(channel_mode) if mode != 'sa' else (0 if channel_mode in _CHANNEL_NAMES else None)
+    fused = _attn_fuse(tensor1, tensor2, mode, sp_code, ch_code)
+    if fused is not None:
+        return fused
     f_spatial = spatial_fusion(tensor1, tensor2, spatial_mode, softmax=False)
     f_channel = channel_fusion(tensor1, tensor2, channel_mode, softmax=False)
     if mode == 'sa':
@@ -237,3 +297,15 @@ def attention_fusion(tensor1, tensor2, mode='sca', spatial_mode='l1', channel_mo
     if mode == 'sca':
         return (f_spatial + f_channel) / 2.0
     return weighted_fusion(f_spatial, f_channel, f_spatial, f_channel)
+
+
+def softmax_l1_fusion(tensor1, tensor2):
+    """SEDRFuse's strategy (reference core/model.py:271-281): per-pixel weights from the channel-softmax-weighted L1 activity
+    sum_c softmax_c(|x|) |x| of each source -- spatial_fusion with the kernels' internal pooling code 5"""
+    fused = _attn_fuse(tensor1, tensor2, 'sa', T.AF_SPATIAL_SOFTMAX_L1, 0)
+    if fused is not None:
+        return fused
+    a1, a2 = torch.abs(tensor1), torch.abs(tensor2)
+    s1 = spatial_pooling(torch.softmax(a1, dim=1) * a1, mode='sum')
+    s2 = spatial_pooling(torch.softmax(a2, dim=1) * a2, mode='sum')
+    return weighted_fusion(tensor1, tensor2, s1, s2)

@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from .block import *
 from .fusion import *
+from .fusion import softmax_l1_fusion
 
 __all__ = ['DeepFuse', 'DBNet', 'SEDRFuse', 'UNFusion', 'Res2Fusion', 'MAFusion', 'IFCNN', 'DIFNet', 'PMGI']
 
@@ -86,11 +87,8 @@ class SEDRFuse(nn.Module):
         return c1, c2, self.encode[3](self.encode[2](c2))
 
     def fusion(self, feat1, feat2):
-        # channel-softmax-weighted L1 activity of each source -> per-pixel weights (tensor-level composition)
-        a1, a2 = torch.abs(feat1), torch.abs(feat2)
-        s1 = spatial_pooling(torch.softmax(a1, dim=1) * a1, mode='sum')
-        s2 = spatial_pooling(torch.softmax(a2, dim=1) * a2, mode='sum')
-        return weighted_fusion(feat1, feat2, s1, s2)
+        # channel-softmax-weighted L1 activity of each source -> per-pixel weights: 'sa' on the fused attention-fusion kernels
+        return softmax_l1_fusion(feat1, feat2)
 
     def decoder(self, f_conv1, f_conv2, f_res):
         f1 = _relu_sum(f_conv2, self.decode[0](f_res))

@@ -176,6 +176,9 @@ SIGNATURES = {
     "mmif_nonlocal_channel_bwd": (_i32, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
     "mmif_fuse_join_fwd": (_i32, [_vp] * 7 + [_i32, _sz, _vp]),
     "mmif_fuse_join_bwd": (_i32, [_vp] * 13 + [_i32, _sz, _vp]),
+    "mmif_attn_fuse_workspace": (_sz, [_i32] * 7),
+    "mmif_attn_fuse_fwd": (_i32, [_vp] * 9 + [_i32] * 7 + [_vp, _sz, _vp]),
+    "mmif_attn_fuse_bwd": (_i32, [_vp] * 11 + [_i32] * 7 + [_vp, _sz, _vp]),
     "mmif_sra_workspace": (_sz, [_i32, _i32, _i32, _i64, _i64]),
     "mmif_sra_fwd": (_i32, [_vp] * 5 + [_i32, _i32, _i32, _i64, _i64, _f32, _vp]),
     "mmif_sra_bwd": (_i32, [_vp] * 9 + [_i32, _i32, _i32, _i64, _i64, _f32, _vp, _sz, _vp]),

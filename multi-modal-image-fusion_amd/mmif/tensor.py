@@ -600,6 +600,54 @@ def fuse_join_bwd(t1, t2, s1, s2, c1, c2, g, mode):
     return tuple(d)
 
 
+# ------------------------------------------------------------------ attention_fusion with tensor-level pooling (plain NCHW fp32; csrc/attn_fuse.hip)
+AF_SPATIAL = {"sum": 0, "mean": 1, "l1": 2, "l2": 3, "linf": 4}
+AF_SPATIAL_SOFTMAX_L1 = 5   # internal: SEDRFuse's sum_c softmax_c(|x|) |x|
+AF_CHANNEL = {"avg": 0, "max": 1}
+
+
+def attn_fuse_supported(t1, t2):
+    """two CUDA fp32 [B,C,H,W] tensors of equal shape inside the kernels' limits (include/mmif.h); everything else stays on the composition"""
+    return (t1.is_cuda and t2.is_cuda and t1.dtype == t2.dtype == torch.float32 and t1.dim() == 4 and t1.shape == t2.shape
+            and 1 <= t1.shape[0] <= 65535 and 1 <= t1.shape[1] <= 65535 and t1.shape[2] >= 1 and t1.shape[3] >= 1
+            and t1.shape[2] * t1.shape[3] < (1 << 30))
+
+
+def _attn_fuse_workspace(t1, mode, spatial_mode, channel_mode):
+    n, c, h, w = t1.shape
+    nbytes = lib.mmif_attn_fuse_workspace(n, c, h, w, mode, spatial_mode, channel_mode)
+    if nbytes == 0:
+        raise _lib.MmifError(f"attn_fuse_workspace: {lib.mmif_last_error().decode()}")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=t1.device)
+
+
+def attn_fuse_fwd(t1, t2, mode, spatial_mode, channel_mode):
+    """mode: JOIN_MODES code; spatial_mode / channel_mode: AF_* codes (in range even where the mode does not use them).  Returns
+    (out, pools): pools = (s1, s2, c1, c2, ci1, ci2), what attn_fuse_bwd needs, None where the mode has no such pool"""
+    _f32c(t1, "t1"), _f32c(t2, "t2")
+    n, c, h, w = t1.shape
+    sp, ch = mode != JOIN_MODES["ca"], mode != JOIN_MODES["sa"]
+    new = lambda use, shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=t1.device) if use else None
+    pools = (new(sp, (n, h * w)), new(sp, (n, h * w)), new(ch, (n, c)), new(ch, (n, c)),
+             new(ch and channel_mode == AF_CHANNEL["max"], (n, c), torch.int32), new(ch and channel_mode == AF_CHANNEL["max"], (n, c), torch.int32))
+    out = torch.empty_like(t1)
+    ws = _attn_fuse_workspace(t1, mode, spatial_mode, channel_mode)
+    check(lib.mmif_attn_fuse_fwd(_ptr(t1), _ptr(t2), _ptr(out), *(_ptr(t) for t in pools), n, c, h, w, mode, spatial_mode, channel_mode, _ptr(ws),
+                                 ws.numel() * 4, stream_ptr()), "attn_fuse_fwd")
+    return out, pools
+
+
+def attn_fuse_bwd(t1, t2, pools, g, mode, spatial_mode, channel_mode):
+    """returns (dt1, dt2)"""
+    _f32c(g, "g")
+    n, c, h, w = t1.shape
+    dt1, dt2 = torch.empty_like(t1), torch.empty_like(t1)
+    ws = _attn_fuse_workspace(t1, mode, spatial_mode, channel_mode)
+    check(lib.mmif_attn_fuse_bwd(_ptr(t1), _ptr(t2), *(_ptr(t) for t in pools), _ptr(g), _ptr(dt1), _ptr(dt2), n, c, h, w, mode, spatial_mode,
+                                 channel_mode, _ptr(ws), ws.numel() * 4, stream_ptr()), "attn_fuse_bwd")
+    return dt1, dt2
+
+
 # ------------------------------------------------------------------ spatial-reduction self-attention core (plain NCHW fp32; csrc/attention.hip)
 SRA_MAX_A = 256
 SRA_HEAD_DIMS = (8, 16, 32)
