@@ -520,6 +520,21 @@ int mmif_ssim_loss_mode(const float* img1, const float* img2, const float* imgf,
  * mmif_ssim_loss_mode_workspace(n, h, w, 1). */
 int mmif_ssim_terms(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, float data_range,
                     float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* SSIMLoss(mode, use_padding=True) core/loss.py:42-49, :252-284: every window pass sees the images reflect-padded by k / 2 (torch
+ * 'reflect': the edge pixel is not repeated), so each map is h x w and every count is h * w.  mode 0 'ssim', 1 'w-ssim' (gammas from
+ * the padded sigma means), 2 'ms-ssim' (the pyramid works on the unpadded images; each level's window pass is padded), 3 'msw-ssim'.
+ * The padding is index arithmetic in the tile loader and its adjoint a fold of the border taps in the gradient pass: no padded
+ * image or gradient goes to memory, and the workspace is that of mmif_ssim_loss_mode_workspace for the same mode (mode 0 as mode 1).
+ * Same contract as mmif_ssim_loss_mode.  h, w >= 11 (modes 0, 1, 3); mode 2 needs every level extent ceil(h / 2^l) >= 6, i.e.
+ * h, w >= 81; any other mode or size -> MMIF_EINVAL. */
+size_t mmif_ssim_loss_pad_workspace(int32_t n, int32_t h, int32_t w, int32_t mode);
+int mmif_ssim_loss_pad(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float weight,
+                       float data_range, int32_t mode, float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* mmif_ssim_terms with use_padding=True: means over the h x w maps of the reflect-padded window pass, window 3 | 5 | 7 | 9 | 11,
+ * h, w >= win_size -> out[3][n].  Values only; workspace as mmif_ssim_loss_pad_workspace(n, h, w, 1). */
+int mmif_ssim_terms_pad(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, float data_range,
+                        float* out, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- Fusion-quality metrics of eval.py (core/metric.py:1-491): per-SAMPLE raw terms of fp32 [n][h][w] images holding 0..255
  * values; the per-image and pooled values are finished from them on the host side (core/metric.py of this package).  fp64 block
  * partials + fixed-order second stages: a sample's terms are bit-identical whatever batch it is in.

@@ -3,7 +3,8 @@
 to stock torch ops but must not change results").  Written from the maths of SURVEY Appendix A.4 -- valid / reflect-padded
 correlation with the Gaussian window, clamped variances, the SSIM and contrast maps -- for
 
-  * `use_padding=True` of the SSIM family (reference core/loss.py:42-49: F.pad(img, k // 2, 'reflect') before every window pass),
+  * `use_padding=True` of the SSIM family (reference core/loss.py:42-49: F.pad(img, k // 2, 'reflect') before every window pass) on CPU
+    tensors, on images below the limits of the padded kernels and on the metric side (CUDA fp32 losses run on mmif_ssim_loss_pad),
   * `size_average=False` (per-pixel maps instead of per-sample means, core/loss.py:103-108),
   * images smaller than the window (the reference shrinks the window to min(win, h, w), core/loss.py:67-71),
   * core.metric.calc_ssim with other windows / `full=True` (core/metric.py:316-364).

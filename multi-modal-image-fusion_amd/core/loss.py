@@ -97,6 +97,49 @@ class _ModeLossFn(torch.autograd.Function):
         return ctx.grad * g, None, None, None, None, None
 
 
+_PAD_MODES = {'ssim': 0, 'w-ssim': 1, 'ms-ssim': 2, 'msw-ssim': 3}
+
+
+def _pad_limit(mode):
+    """smallest h, w of mmif_ssim_loss_pad: the 11-tap window; 'ms-ssim' pads a level of ceil(h / 16) pixels by 5"""
+    return 81 if mode == 'ms-ssim' else 11
+
+
+def _pad_on_device(limit, *imgs):
+    """use_padding=True runs on mmif_ssim_loss_pad / mmif_ssim_terms_pad for CUDA fp32 [B,1,H,W] images of at least limit x limit;
+    everything else keeps the stock composition"""
+    x = imgs[-1]
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in imgs) or x.dim() != 4 or x.shape[1] != 1:
+        return False
+    return min(x.shape[-2:]) >= limit
+
+
+class _PadLossFn(torch.autograd.Function):
+    """SSIMLoss(mode, use_padding=True) (reference core/loss.py:42-49, :252-284) on the reflect-padded kernels of csrc/loss_modes.hip;
+    mode: 0 'ssim' | 1 'w-ssim' | 2 'ms-ssim' | 3 'msw-ssim'."""
+
+    @staticmethod
+    def forward(ctx, imgf, img1, img2, mode, weight, data_range):
+        i1, i2, f = _prep(img1, img2, imgf)
+        n, _, h, w = f.shape
+        need = ctx.needs_input_grad[0]
+        out = torch.empty(1, dtype=torch.float32, device=f.device)
+        grad = torch.empty_like(f) if need else None
+        nbytes = lib.mmif_ssim_loss_pad_workspace(n, h, w, mode)
+        ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=f.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(lib.mmif_ssim_loss_pad(p(i1), p(i2), p(f), n, h, w, weight, data_range, mode, p(out), p(grad), p(ws), ws.numel() * 4,
+                                     T.stream_ptr()), "ssim_loss_pad")
+        ctx.grad = grad
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.grad is None:
+            return (None,) * 6
+        return ctx.grad * g, None, None, None, None, None
+
+
 class _TVFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, l2, weight):
@@ -125,30 +168,35 @@ class _TVFn(torch.autograd.Function):
 class SSIM(nn.Module):
     """Structural similarity (reference core/loss.py:163-185): {'ssim', 'cs', 'sigma'} per-sample means of (img1, img2) for a
     window of 3 / 5 / 7 / 9 / 11 taps.  'ssim' with the default 11x11 window is differentiable w.r.t. img2 (the fused image in
-    every use of the reference); 'cs' and 'sigma' are values."""
+    every use of the reference); 'cs' and 'sigma' are values.  use_padding=True (reflect-padded windows, size_average=True) runs on
+    the padded kernels for CUDA fp32 images no smaller than the window, with the same differentiability."""
 
     def __init__(self, win_size=11, data_range=1.0, use_padding=False, size_average=True):
         super(SSIM, self).__init__()
         self.win_size, self.data_range, self.use_padding, self.size_average = win_size, data_range, use_padding, size_average
-        # argument combinations outside the HIP kernels (reflect-padded windows, per-pixel maps, other window sizes) run as stock torch
-        # ops with the reference's results (core/_stock.py; SURVEY 8b)
-        self._stock = win_size not in (3, 5, 7, 9, 11) or bool(use_padding) or not size_average
+        # argument combinations outside the HIP kernels (per-pixel maps, other window sizes; with use_padding: CPU or non-fp32 tensors)
+        # run as stock torch ops with the reference's results (core/_stock.py; SURVEY 8b)
+        self._stock = win_size not in (3, 5, 7, 9, 11) or not size_average
+        self._pad = bool(use_padding)
 
     def forward(self, img1, img2):
-        if self._stock or min(img1.shape[-2:]) < self.win_size:
+        small = min(img1.shape[-2:]) < self.win_size
+        if self._stock or small or (self._pad and not _pad_on_device(self.win_size, img1, img2)):
             return _stock.ssim_terms(img1, img2, self.win_size, self.data_range, self.use_padding, self.size_average, _stock.window(self.win_size))
         i1, i2, _ = _prep(img1, img2, img2)
         n, _, h, w = i1.shape
         out = torch.empty((3, n), dtype=torch.float32, device=i1.device)
         ws = torch.empty(lib.mmif_ssim_loss_mode_workspace(n, h, w, 1) // 4 + 1, dtype=torch.float32, device=i1.device)
         p = lambda t: C.c_void_p(t.data_ptr())
-        check(lib.mmif_ssim_terms(p(i1), p(i2), n, h, w, self.win_size, float(self.data_range), p(out), p(ws), ws.numel() * 4,
-                                  T.stream_ptr()), "ssim_terms")
+        terms = lib.mmif_ssim_terms_pad if self._pad else lib.mmif_ssim_terms
+        check(terms(p(i1), p(i2), n, h, w, self.win_size, float(self.data_range), p(out), p(ws), ws.numel() * 4, T.stream_ptr()),
+              "ssim_terms_pad" if self._pad else "ssim_terms")
         res = {'ssim': out[0], 'cs': out[1], 'sigma': out[2]}
         if self.win_size == 11 and torch.is_grad_enabled() and img2.requires_grad:
             # differentiable path: the batch-1 loss kernel per sample (loss = 1 - S with both sources = img1)
-            res['ssim'] = torch.stack([1.0 - _LossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], 0, 1.0, float(self.data_range), 0)
-                                       for i in range(n)])
+            one = (lambda i: _PadLossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], 0, 1.0, float(self.data_range))) if self._pad else \
+                (lambda i: _LossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], 0, 1.0, float(self.data_range), 0))
+            res['ssim'] = torch.stack([1.0 - one(i) for i in range(n)])
         return res
 
 
@@ -159,12 +207,14 @@ class MS_SSIM(nn.Module):
     def __init__(self, win_size=11, data_range=1.0, use_padding=False, size_average=True):
         super(MS_SSIM, self).__init__()
         self.win_size, self.data_range, self.use_padding, self.size_average = win_size, data_range, use_padding, size_average
-        self._stock = win_size != 11 or bool(use_padding) or not size_average      # (core/_stock.py: stock torch ops, same results)
+        self._stock = win_size != 11 or not size_average      # (core/_stock.py: stock torch ops, same results)
+        self._pad = bool(use_padding)                          # reflect-padded windows: the padded kernels, images >= 81 x 81
 
     def forward(self, img1, img2):
-        if self._stock:
+        if self._stock or (self._pad and not _pad_on_device(_pad_limit('ms-ssim'), img1, img2)):
             return _stock.msssim(img1, img2, self.win_size, self.data_range, self.use_padding, self.size_average)
-        vals = [1.0 - _ModeLossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], _SSIM_MODES['ms-ssim'], 1.0, float(self.data_range))
+        fn, mode = (_PadLossFn, _PAD_MODES['ms-ssim']) if self._pad else (_ModeLossFn, _SSIM_MODES['ms-ssim'])
+        vals = [1.0 - fn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], mode, 1.0, float(self.data_range))
                 for i in range(img1.shape[0])]
         return torch.stack(vals)
 
@@ -176,11 +226,14 @@ class MSW_SSIM(nn.Module):
     def __init__(self, win_sizes=(11, 9, 7, 5, 3), data_range=1.0, use_padding=False, size_average=False):
         super(MSW_SSIM, self).__init__()
         self.win_sizes, self.data_range, self.use_padding, self.size_average = tuple(win_sizes), data_range, use_padding, size_average
-        self._stock = tuple(win_sizes) != (11, 9, 7, 5, 3) or bool(use_padding) or bool(size_average)   # (core/_stock.py)
+        self._stock = tuple(win_sizes) != (11, 9, 7, 5, 3) or bool(size_average)   # (core/_stock.py)
+        self._pad = bool(use_padding)
 
     def forward(self, img1, img2, imgf):
-        if self._stock:
+        if self._stock or (self._pad and not _pad_on_device(_pad_limit('msw-ssim'), img1, img2, imgf)):
             return _stock.mswssim(img1, img2, imgf, self.win_sizes, self.data_range, self.use_padding, self.size_average)
+        if self._pad:
+            return 1.0 - _PadLossFn.apply(imgf, img1, img2, _PAD_MODES['msw-ssim'], 1.0, float(self.data_range))
         return 1.0 - _ModeLossFn.apply(imgf, img1, img2, _SSIM_MODES['msw-ssim'], 1.0, float(self.data_range))
 
 
@@ -190,8 +243,11 @@ class SSIMLoss(nn.Module):
         self.mode, self.data_range, self.use_padding, self.weight = mode, data_range, use_padding, weight
 
     def forward(self, img1, img2, imgf):
-        if self.use_padding and (self.mode == 'ssim' or self.mode in _SSIM_MODES):
-            # reflect-padded windows (core/loss.py:42-49) are not a HIP kernel: stock torch ops, the reference's results (core/_stock.py)
+        if self.use_padding and self.mode in _PAD_MODES:
+            # reflect-padded windows (core/loss.py:42-49): the padded kernels of csrc/loss_modes.hip; CPU tensors, other dtypes and images
+            # below their limits run as stock torch ops with the reference's results (core/_stock.py)
+            if _pad_on_device(_pad_limit(self.mode), img1, img2, imgf):
+                return _PadLossFn.apply(imgf, img1, img2, _PAD_MODES[self.mode], float(self.weight), float(self.data_range))
             return _stock.ssim_loss(self.mode, img1, img2, imgf, self.data_range, True, self.weight)
         if self.mode == 'ssim':
             return _LossFn.apply(imgf, img1, img2, 0, float(self.weight), float(self.data_range), 0)
@@ -318,6 +374,8 @@ class FusionLoss(nn.Module):
         super().__init__()
         if getattr(loss_fn1, 'mode', 'ssim') != 'ssim':
             raise ValueError("FusionLoss fuses SSIMLoss('ssim') only; use the modules separately for the other SSIM modes")
+        if getattr(loss_fn1, 'use_padding', False):
+            raise ValueError("FusionLoss fuses SSIMLoss('ssim') without padding only; use the modules separately for use_padding=True")
         for m in (pixel_mode, grad_mode):
             if m not in ('max', 'avg'):
                 raise ValueError("only supports 'max' and 'avg' modes.")

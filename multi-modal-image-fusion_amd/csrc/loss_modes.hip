@@ -40,7 +40,9 @@ static void make_window(WinK& w, int k) {
 // per map pixel and pair p (x1|x2 vs f): Q_p = ssim or cs; effective weight g_p = c_p * (w_p ? w_p[sample] : 1) * (pixel gamma?)
 // partial[q][sample][block]: q0 = sum g_1 Q_1, q1 = sum g_2 Q_2, q2 = sum sigma_1, q3 = sum sigma_2   (sigma = clamp(var x, 1e-4))
 // maps (optional) [4][n][Hm][Wm]: A = g1 A1 + g2 A2, B = g1 B1 + g2 B2, C1 = g1 C1', C2 = g2 C2'
-template <int WIN>
+// PAD (use_padding=True, core/loss.py:42-49): the window pass sees the images reflect-padded by P = WIN / 2, so the map is H x W and
+// the tile loader reads image pixel (reflect(y - P), reflect(x - P)); nothing after the loader changes.
+template <int WIN, int PAD>
 __global__ __launch_bounds__(256) void ssimx_stats_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
                                                           const float* __restrict__ f, int H, int W, WinK win, float C1, float C2,
                                                           float ca, float cb, const float* __restrict__ wa, const float* __restrict__ wb,
@@ -50,15 +52,24 @@ __global__ __launch_bounds__(256) void ssimx_stats_kernel(const float* __restric
     __shared__ float in[3][LIN][LIN + 1];
     __shared__ float hb[8][LIN][MT_ + 1];
     __shared__ float red[16];
-    const int Hm = H - WIN + 1, Wm = W - WIN + 1;
+    const int Hm = PAD ? H : H - WIN + 1, Wm = PAD ? W : W - WIN + 1;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int mx0 = (blockIdx.x % tiles_x) * MT_, my0 = (blockIdx.x / tiles_x) * MT_;
     const int in_ = blockIdx.y;
     const long long ibase = (long long)in_ * H * W;
     for (int e = tid; e < LIN * LIN; e += 256) {
         const int py = e / LIN, px = e % LIN;
-        const int y = my0 + py, x = mx0 + px;
-        const bool ok = (y < H) && (x < W);
+        int y = my0 + py, x = mx0 + px;
+        bool ok = (y < H) && (x < W);
+        if (PAD) {   // padded row my0 + py mirrors image row reflect(my0 + py - P); P < H, W, so one reflection lands inside
+            constexpr int P = WIN / 2;
+            ok = (y < H + 2 * P) && (x < W + 2 * P);
+            y -= P;
+            x -= P;
+            y = y < 0 ? -y : (y >= H ? 2 * (H - 1) - y : y);
+            x = x < 0 ? -x : (x >= W ? 2 * (W - 1) - x : x);
+            if (!ok) y = x = 0;
+        }
         const long long i = ibase + (long long)y * W + x;
         in[0][py][px] = ok ? x1[i] : 0.f;
         in[1][py][px] = ok ? x2[i] : 0.f;
@@ -156,22 +167,49 @@ __global__ __launch_bounds__(256) void ssimx_stats_kernel(const float* __restric
 
 // ------------------------------------------------------------------ pass 2: adjoint correlation
 // grad[y][x] (+)= scale * ( (G^T*A) + 2 f (G^T*B) + x1 (G^T*C1) + x2 (G^T*C2) ),  (G^T*M)[y][x] = sum_{u,v} G[u][v] M[y-u][x-v]
+// PAD: the adjoint correlation runs over the padded domain and is folded back through the reflect padding.  A padded pixel holds the
+// image pixel it mirrors, so f, x1 and x2 factor out and image pixel (y, x) sums (G^T*M)(Y, X) over its pre-images; per axis
+// pre(c) = {c}, -c for 1 <= c <= P, 2 (n - 1) - c for n - 1 - P <= c <= n - 2 (all three for some c when n <= 2 P + 1).  Correlation
+// and fold are both separable, so each axis is one banded operator  out[c] = sum_{m = c - P}^{c + P} T[c][m] M[m]  with
+// T[c][m] = sum_{Y in pre(c)} g[Y + P - m]  (taps outside 0..WIN-1 count zero): the same two LDS passes with a halo of P on both
+// sides, and fold_tap() in place of the plain tap in the blocks that hold a border column / row.  No padded-domain buffer exists.
 template <int WIN>
+__device__ __forceinline__ float fold_tap(const float* __restrict__ wl, int c, int j, int n) {
+    constexpr int P = WIN / 2;
+    float t = wl[WIN - 1 - j];                       // Y = c, m = c - P + j
+    const int lo = 2 * P - 2 * c - j;                // Y = -c
+    if (c >= 1 && c <= P && lo >= 0) t += wl[lo];
+    const int hi = 2 * (n - 1 - c) + 2 * P - j;      // Y = 2 (n - 1) - c
+    if (c >= n - 1 - P && c <= n - 2 && hi < WIN) t += wl[hi];
+    return t;
+}
+
+template <int WIN, int PAD>
 __global__ __launch_bounds__(256) void ssimx_grad_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
                                                          const float* __restrict__ f, int H, int W, WinK win,
                                                          const float* __restrict__ maps, float scale, int accumulate,
                                                          float* __restrict__ grad, int tiles_x) {
     constexpr int LIN = MT_ + WIN - 1;
+    constexpr int HALO = PAD ? WIN / 2 : WIN - 1;    // map rows / columns before the tile that reach it
     __shared__ float in[4][LIN][LIN + 1];
     __shared__ float hb[4][LIN][MT_ + 1];
-    const int Hm = H - WIN + 1, Wm = W - WIN + 1;
+    __shared__ float wl[WIN];
+    const int Hm = PAD ? H : H - WIN + 1, Wm = PAD ? W : W - WIN + 1;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int x0 = (blockIdx.x % tiles_x) * MT_, y0 = (blockIdx.x / tiles_x) * MT_;
     const int in_ = blockIdx.y;
     const long long msz = (long long)gridDim.y * Hm * Wm;
+    // block-uniform: does the tile hold a column / row with more than one pre-image?  (interior tiles run the plain taps)
+    const bool fold_x = PAD && (x0 <= WIN / 2 || x0 + MT_ - 1 >= W - 1 - WIN / 2);
+    const bool fold_y = PAD && (y0 <= WIN / 2 || y0 + MT_ - 1 >= H - 1 - WIN / 2);
+    if (PAD) {
+#pragma unroll
+        for (int k = 0; k < WIN; ++k)
+            if (tid == k) wl[k] = win.t[k];
+    }
     for (int e = tid; e < LIN * LIN; e += 256) {
         const int py = e / LIN, px = e % LIN;
-        const int my = y0 - (WIN - 1) + py, mx = x0 - (WIN - 1) + px;
+        const int my = y0 - HALO + py, mx = x0 - HALO + px;
         const bool ok = my >= 0 && my < Hm && mx >= 0 && mx < Wm;
         const long long mi = ((long long)in_ * Hm + my) * Wm + mx;
 #pragma unroll
@@ -181,22 +219,40 @@ __global__ __launch_bounds__(256) void ssimx_grad_kernel(const float* __restrict
     for (int e = tid; e < LIN * MT_; e += 256) {
         const int py = e / MT_, px = e % MT_;
         float s[4] = {0.f, 0.f, 0.f, 0.f};
+        if (fold_x) {
 #pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const float wk = win.t[k];
+            for (int k = 0; k < WIN; ++k) {
+                const float wk = fold_tap<WIN>(wl, x0 + px, (WIN - 1) - k, W);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) s[q] = fmaf(wk, in[q][py][px + (WIN - 1) - k], s[q]);
+                for (int q = 0; q < 4; ++q) s[q] = fmaf(wk, in[q][py][px + (WIN - 1) - k], s[q]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < WIN; ++k) {
+                const float wk = win.t[k];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) s[q] = fmaf(wk, in[q][py][px + (WIN - 1) - k], s[q]);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) hb[q][py][px] = s[q];
     }
     __syncthreads();
     float m[4] = {0.f, 0.f, 0.f, 0.f};
+    if (fold_y) {
 #pragma unroll
-    for (int k = 0; k < WIN; ++k) {
-        const float wk = win.t[k];
+        for (int k = 0; k < WIN; ++k) {
+            const float wk = fold_tap<WIN>(wl, y0 + ty, (WIN - 1) - k, H);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) m[q] = fmaf(wk, hb[q][ty + (WIN - 1) - k][tx], m[q]);
+            for (int q = 0; q < 4; ++q) m[q] = fmaf(wk, hb[q][ty + (WIN - 1) - k][tx], m[q]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < WIN; ++k) {
+            const float wk = win.t[k];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) m[q] = fmaf(wk, hb[q][ty + (WIN - 1) - k][tx], m[q]);
+        }
     }
     const int y = y0 + ty, x = x0 + tx;
     if (y < H && x < W) {
@@ -340,25 +396,25 @@ struct SsimArgs {
     hipStream_t st;
 };
 
-template <int WIN>
+template <int WIN, int PAD = 0>
 static int run_stats(const SsimArgs& a, float ca, float cb, const float* wa, const float* wb, int pix, int cs, float* maps,
                      float* partial, float* sums) {
     WinK win;
     make_window(win, WIN);
-    const int Hm = a.h - WIN + 1, Wm = a.w - WIN + 1;
+    const int Hm = PAD ? a.h : a.h - WIN + 1, Wm = PAD ? a.w : a.w - WIN + 1;
     const int tmx = cdiv(Wm, MT_), tmy = cdiv(Hm, MT_);
-    hipLaunchKernelGGL((ssimx_stats_kernel<WIN>), dim3(tmx * tmy, a.n), dim3(256), 0, a.st, a.x1, a.x2, a.f, a.h, a.w, win, a.C1, a.C2, ca,
+    hipLaunchKernelGGL((ssimx_stats_kernel<WIN, PAD>), dim3(tmx * tmy, a.n), dim3(256), 0, a.st, a.x1, a.x2, a.f, a.h, a.w, win, a.C1, a.C2, ca,
                        cb, wa, wb, pix, cs, maps, partial, tmx);
     if (int rc = check_launch("ssimx_stats")) return rc;
     hipLaunchKernelGGL(row_sums_kernel, dim3(4 * a.n), dim3(256), 0, a.st, partial, tmx * tmy, sums);
     return check_launch("ssimx_row_sums");
 }
-template <int WIN>
+template <int WIN, int PAD = 0>
 static int run_grad(const SsimArgs& a, const float* maps, float scale, int accumulate, float* grad) {
     WinK win;
     make_window(win, WIN);
     const int tx = cdiv(a.w, MT_), ty = cdiv(a.h, MT_);
-    hipLaunchKernelGGL((ssimx_grad_kernel<WIN>), dim3(tx * ty, a.n), dim3(256), 0, a.st, a.x1, a.x2, a.f, a.h, a.w, win, maps, scale,
+    hipLaunchKernelGGL((ssimx_grad_kernel<WIN, PAD>), dim3(tx * ty, a.n), dim3(256), 0, a.st, a.x1, a.x2, a.f, a.h, a.w, win, maps, scale,
                        accumulate, grad, tx);
     return check_launch("ssimx_grad");
 }
@@ -386,19 +442,11 @@ extern "C" size_t mmif_ssim_loss_mode_workspace(int32_t n, int32_t h, int32_t w,
     return fl * sizeof(float);
 }
 
-extern "C" int mmif_ssim_loss_mode(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float weight,
-                                   float data_range, int32_t mode, float* loss_out, float* grad_out, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-    if (mode < 1 || mode > 3) {
-        set_error("only supported ['ssim', 'w-ssim', 'ms-ssim', 'msw-ssim'] mode");   // core/loss.py:279-282 ('ssim': mmif_ssim_loss)
-        return MMIF_EINVAL;
-    }
-    MMIF_REQUIRE(img1 && img2 && imgf && loss_out && workspace, "ssim_loss_mode: NULL argument");
-    MMIF_REQUIRE(n > 0 && h >= 11 && w >= 11, "ssim_loss_mode: image smaller than the 11x11 window (%dx%d)", h, w);
-    if (workspace_bytes < mmif_ssim_loss_mode_workspace(n, h, w, mode)) {
-        set_error("ssim_loss_mode: workspace too small");
-        return MMIF_EWORKSPACE;
-    }
+// The modes on either geometry; the entry points below have checked mode, sizes and workspace.  PAD: reflect-padded window passes,
+// every map h x w (counts h * w); mode 0 ('ssim', 0.5 / 0.5 weights) is reached with PAD only -- unpadded it is mmif_ssim_loss.
+template <int PAD>
+static int ssim_modes_run(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float weight,
+                          float data_range, int32_t mode, float* loss_out, float* grad_out, void* workspace, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
     const size_t tiles = (size_t)cdiv(h, MT_) * cdiv(w, MT_);
@@ -410,29 +458,37 @@ extern "C" int mmif_ssim_loss_mode(const float* img1, const float* img2, const f
     float* wts = vals + 10 * n;
     float* maps = wts + 10 * n;
     SsimArgs a{img1, img2, imgf, n, h, w, C1, C2, st};
+    if (mode == 0) {   // ssim (PAD only): weight * (1 - (mean S1 + mean S2) / 2)
+        const float cnt = (float)h * (float)w;
+        if (int rc = run_stats<11, PAD>(a, 1.f, 1.f, nullptr, nullptr, 0, 0, grad_out ? maps : nullptr, partial, sums)) return rc;
+        hipLaunchKernelGGL(value_finish_kernel, dim3(1), dim3(64), 0, st, sums, n, 1.f / ((float)n * cnt), weight, 0.5f, 1, loss_out);
+        if (int rc = check_launch("ssim_pad_finish")) return rc;
+        if (grad_out) return run_grad<11, PAD>(a, maps, -weight * 0.5f / ((float)n * cnt), 0, grad_out);
+        return MMIF_OK;
+    }
     if (mode == 1) {   // w-ssim
-        const float cnt = (float)(h - 10) * (float)(w - 10);
-        if (int rc = run_stats<11>(a, 1.f, 1.f, nullptr, nullptr, 0, 0, nullptr, partial, sums)) return rc;   // sigma means
+        const float cnt = PAD ? (float)h * (float)w : (float)(h - 10) * (float)(w - 10);
+        if (int rc = run_stats<11, PAD>(a, 1.f, 1.f, nullptr, nullptr, 0, 0, nullptr, partial, sums)) return rc;   // sigma means
         hipLaunchKernelGGL(wssim_gamma_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, sums, n, 1.f / cnt, wa, wb);
         if (int rc = check_launch("wssim_gamma")) return rc;
-        if (int rc = run_stats<11>(a, 1.f, 1.f, wa, wb, 0, 0, grad_out ? maps : nullptr, partial, sums)) return rc;
+        if (int rc = run_stats<11, PAD>(a, 1.f, 1.f, wa, wb, 0, 0, grad_out ? maps : nullptr, partial, sums)) return rc;
         hipLaunchKernelGGL(value_finish_kernel, dim3(1), dim3(64), 0, st, sums, n, 1.f / ((float)n * cnt), weight, 1.f, 1, loss_out);
         if (int rc = check_launch("wssim_finish")) return rc;
-        if (grad_out) return run_grad<11>(a, maps, -weight / ((float)n * cnt), 0, grad_out);
+        if (grad_out) return run_grad<11, PAD>(a, maps, -weight / ((float)n * cnt), 0, grad_out);
         return MMIF_OK;
     }
     if (mode == 3) {   // msw-ssim
         int first = 1;
-#define MSW_STEP(K)                                                                                                              \
-    {                                                                                                                            \
-        const float cnt = (float)(h - K + 1) * (float)(w - K + 1);                                                               \
-        if (int rc = run_stats<K>(a, 1.f, 1.f, nullptr, nullptr, 1, 0, grad_out ? maps : nullptr, partial, sums)) return rc;      \
-        hipLaunchKernelGGL(value_finish_kernel, dim3(1), dim3(64), 0, st, sums, n, 1.f / ((float)n * cnt), weight, 0.2f, first, \
-                           loss_out);                                                                                            \
-        if (int rc = check_launch("mswssim_finish")) return rc;                                                                  \
-        if (grad_out)                                                                                                            \
-            if (int rc = run_grad<K>(a, maps, -weight * 0.2f / ((float)n * cnt), first ? 0 : 1, grad_out)) return rc;            \
-        first = 0;                                                                                                               \
+#define MSW_STEP(K)                                                                                                                   \
+    {                                                                                                                                 \
+        const float cnt = PAD ? (float)h * (float)w : (float)(h - K + 1) * (float)(w - K + 1);                                        \
+        if (int rc = run_stats<K, PAD>(a, 1.f, 1.f, nullptr, nullptr, 1, 0, grad_out ? maps : nullptr, partial, sums)) return rc;      \
+        hipLaunchKernelGGL(value_finish_kernel, dim3(1), dim3(64), 0, st, sums, n, 1.f / ((float)n * cnt), weight, 0.2f, first,      \
+                           loss_out);                                                                                                 \
+        if (int rc = check_launch("mswssim_finish")) return rc;                                                                       \
+        if (grad_out)                                                                                                                 \
+            if (int rc = run_grad<K, PAD>(a, maps, -weight * 0.2f / ((float)n * cnt), first ? 0 : 1, grad_out)) return rc;            \
+        first = 0;                                                                                                                    \
     }
         MSW_STEP(11) MSW_STEP(9) MSW_STEP(7) MSW_STEP(5) MSW_STEP(3)
 #undef MSW_STEP
@@ -446,7 +502,7 @@ extern "C" int mmif_ssim_loss_mode(const float* img1, const float* img2, const f
         hs[l] = (hs[l - 1] + 1) / 2;
         wsz[l] = (wsz[l - 1] + 1) / 2;
     }
-    MMIF_REQUIRE(hs[4] >= 11 && wsz[4] >= 11, "ssim_loss_mode: ms-ssim needs images of at least 161x161 (11x11 window on level 4); got %dx%d", h, w);
+    if (!PAD) MMIF_REQUIRE(hs[4] >= 11 && wsz[4] >= 11, "ssim_loss_mode: ms-ssim needs images of at least 161x161 (11x11 window on level 4); got %dx%d", h, w);
     float* pyr = maps + 4 * (size_t)n * h * w;
     const float* lx1[5] = {img1};
     const float* lx2[5] = {img2};
@@ -472,9 +528,9 @@ extern "C" int mmif_ssim_loss_mode(const float* img1, const float* img2, const f
     const float msw[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
     for (int l = 0; l < 5; ++l) {
         meta.w[l] = msw[l];
-        meta.inv_nmap[l] = 1.f / ((float)(hs[l] - 10) * (float)(wsz[l] - 10));
+        meta.inv_nmap[l] = 1.f / (PAD ? (float)hs[l] * (float)wsz[l] : (float)(hs[l] - 10) * (float)(wsz[l] - 10));
         SsimArgs al{lx1[l], lx2[l], lf[l], n, hs[l], wsz[l], C1, C2, st};
-        if (int rc = run_stats<11>(al, 1.f, 1.f, nullptr, nullptr, 0, l < 4 ? 1 : 0, nullptr, partial, sums)) return rc;
+        if (int rc = run_stats<11, PAD>(al, 1.f, 1.f, nullptr, nullptr, 0, l < 4 ? 1 : 0, nullptr, partial, sums)) return rc;
         // vals[p][l][b] <- sums[p][b]
         (void)hipMemcpyAsync(vals + (0 * 5 + l) * n, sums, n * sizeof(float), hipMemcpyDeviceToDevice, st);
         (void)hipMemcpyAsync(vals + (1 * 5 + l) * n, sums + n, n * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -484,8 +540,8 @@ extern "C" int mmif_ssim_loss_mode(const float* img1, const float* img2, const f
     if (!grad_out) return MMIF_OK;
     for (int l = 4; l >= 0; --l) {
         SsimArgs al{lx1[l], lx2[l], lf[l], n, hs[l], wsz[l], C1, C2, st};
-        if (int rc = run_stats<11>(al, 1.f, 1.f, wts + (0 * 5 + l) * n, wts + (1 * 5 + l) * n, 0, l < 4 ? 1 : 0, maps, partial, sums)) return rc;
-        if (int rc = run_grad<11>(al, maps, 1.f, 0, lg[l])) return rc;
+        if (int rc = run_stats<11, PAD>(al, 1.f, 1.f, wts + (0 * 5 + l) * n, wts + (1 * 5 + l) * n, 0, l < 4 ? 1 : 0, maps, partial, sums)) return rc;
+        if (int rc = run_grad<11, PAD>(al, maps, 1.f, 0, lg[l])) return rc;
         if (l < 4) {
             hipLaunchKernelGGL(avg_pool_pad_bwd_kernel, dim3(ew_grid((long long)n * hs[l] * wsz[l])), dim3(256), 0, st, lg[l + 1], lg[l], n,
                                hs[l], wsz[l]);
@@ -495,6 +551,45 @@ extern "C" int mmif_ssim_loss_mode(const float* img1, const float* img2, const f
     return MMIF_OK;
 }
 
+extern "C" int mmif_ssim_loss_mode(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float weight,
+                                   float data_range, int32_t mode, float* loss_out, float* grad_out, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    if (mode < 1 || mode > 3) {
+        set_error("only supported ['ssim', 'w-ssim', 'ms-ssim', 'msw-ssim'] mode");   // core/loss.py:279-282 ('ssim': mmif_ssim_loss)
+        return MMIF_EINVAL;
+    }
+    MMIF_REQUIRE(img1 && img2 && imgf && loss_out && workspace, "ssim_loss_mode: NULL argument");
+    MMIF_REQUIRE(n > 0 && h >= 11 && w >= 11, "ssim_loss_mode: image smaller than the 11x11 window (%dx%d)", h, w);
+    if (workspace_bytes < mmif_ssim_loss_mode_workspace(n, h, w, mode)) {
+        set_error("ssim_loss_mode: workspace too small");
+        return MMIF_EWORKSPACE;
+    }
+    return ssim_modes_run<0>(img1, img2, imgf, n, h, w, weight, data_range, mode, loss_out, grad_out, workspace, stream);
+}
+
+// use_padding=True: the maps are h x w, which the 4*n*h*w floats of the unpadded layout already hold; mode 0 takes mode 1's layout
+extern "C" size_t mmif_ssim_loss_pad_workspace(int32_t n, int32_t h, int32_t w, int32_t mode) {
+    return mmif_ssim_loss_mode_workspace(n, h, w, mode == 2 ? 2 : 1);
+}
+
+extern "C" int mmif_ssim_loss_pad(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float weight,
+                                  float data_range, int32_t mode, float* loss_out, float* grad_out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    if (mode < 0 || mode > 3) {
+        set_error("only supported ['ssim', 'w-ssim', 'ms-ssim', 'msw-ssim'] mode");   // core/loss.py:279-282
+        return MMIF_EINVAL;
+    }
+    MMIF_REQUIRE(img1 && img2 && imgf && loss_out && workspace, "ssim_loss_pad: NULL argument");
+    MMIF_REQUIRE(n > 0 && h >= 11 && w >= 11, "ssim_loss_pad: image smaller than the 11x11 window (%dx%d)", h, w);
+    // F.pad(..., 'reflect') needs 5 < extent on every pyramid level: ceil(h / 16) >= 6
+    MMIF_REQUIRE(mode != 2 || (h >= 81 && w >= 81), "ssim_loss_pad: ms-ssim needs images of at least 81x81 (reflect padding by 5 on level 4); got %dx%d", h, w);
+    if (workspace_bytes < mmif_ssim_loss_pad_workspace(n, h, w, mode)) {
+        set_error("ssim_loss_pad: workspace too small");
+        return MMIF_EWORKSPACE;
+    }
+    return ssim_modes_run<1>(img1, img2, imgf, n, h, w, weight, data_range, mode, loss_out, grad_out, workspace, stream);
+}
+
 // out[q][b] = sums[qsel][b] * scale  (tiny gather used by mmif_ssim_terms)
 __global__ void pick_row_kernel(const float* __restrict__ sums, int n, int qsel, float scale, float* __restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -502,14 +597,15 @@ __global__ void pick_row_kernel(const float* __restrict__ sums, int n, int qsel,
 }
 
 /* calc_ssim core/loss.py:52-110 with size_average=True: per-sample means of the ssim map, the cs map and the clamped source
- * variance sigma of (img1, img2) for a window of 3/5/7/9/11 taps -> out[3][n] (device).  Values only. */
-extern "C" int mmif_ssim_terms(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, float data_range,
-                               float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    MMIF_REQUIRE(img1 && img2 && out && workspace, "ssim_terms: NULL argument");
-    MMIF_REQUIRE(win_size == 3 || win_size == 5 || win_size == 7 || win_size == 9 || win_size == 11, "ssim_terms: win_size must be 3, 5, 7, 9 or 11 (got %d)", win_size);
-    MMIF_REQUIRE(n > 0 && h >= win_size && w >= win_size, "ssim_terms: image smaller than the window (%dx%d)", h, w);
+ * variance sigma of (img1, img2) for a window of 3/5/7/9/11 taps -> out[3][n] (device).  Values only.  PAD: use_padding=True. */
+template <int PAD>
+static int ssim_terms_run(const char* who, const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size,
+                          float data_range, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    MMIF_REQUIRE(img1 && img2 && out && workspace, "%s: NULL argument", who);
+    MMIF_REQUIRE(win_size == 3 || win_size == 5 || win_size == 7 || win_size == 9 || win_size == 11, "%s: win_size must be 3, 5, 7, 9 or 11 (got %d)", who, win_size);
+    MMIF_REQUIRE(n > 0 && h >= win_size && w >= win_size, "%s: image smaller than the window (%dx%d)", who, h, w);
     if (workspace_bytes < mmif_ssim_loss_mode_workspace(n, h, w, 1)) {
-        set_error("ssim_terms: workspace too small");
+        set_error("%s: workspace too small", who);
         return MMIF_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -518,15 +614,15 @@ extern "C" int mmif_ssim_terms(const float* img1, const float* img2, int32_t n, 
     float* partial = (float*)workspace;
     float* sums = partial + 4 * n * tiles;
     SsimArgs a{img1, img1, img2, n, h, w, C1, C2, st};   // pair 1 = (img1, img2); pair 2 unused
-    const float inv = 1.f / ((float)(h - win_size + 1) * (float)(w - win_size + 1));
+    const float inv = 1.f / (PAD ? (float)h * (float)w : (float)(h - win_size + 1) * (float)(w - win_size + 1));
     for (int cs = 0; cs < 2; ++cs) {
         int rc;
         switch (win_size) {
-            case 3: rc = run_stats<3>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            case 5: rc = run_stats<5>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            case 7: rc = run_stats<7>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            case 9: rc = run_stats<9>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            default: rc = run_stats<11>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
+            case 3: rc = run_stats<3, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
+            case 5: rc = run_stats<5, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
+            case 7: rc = run_stats<7, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
+            case 9: rc = run_stats<9, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
+            default: rc = run_stats<11, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
         }
         if (rc) return rc;
         hipLaunchKernelGGL(pick_row_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, sums, n, 0, inv, out + cs * n);
@@ -534,6 +630,16 @@ extern "C" int mmif_ssim_terms(const float* img1, const float* img2, int32_t n, 
         if (int rc2 = check_launch("ssim_terms pick")) return rc2;
     }
     return MMIF_OK;
+}
+
+extern "C" int mmif_ssim_terms(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, float data_range,
+                               float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return ssim_terms_run<0>("ssim_terms", img1, img2, n, h, w, win_size, data_range, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mmif_ssim_terms_pad(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, float data_range,
+                                   float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return ssim_terms_run<1>("ssim_terms_pad", img1, img2, n, h, w, win_size, data_range, out, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mmif_tv_loss_workspace(void) { return 4096 * sizeof(float); }

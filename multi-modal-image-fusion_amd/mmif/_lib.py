@@ -204,6 +204,9 @@ SIGNATURES = {
     "mmif_ssim_loss_mode_workspace": (_sz, [_i32, _i32, _i32, _i32]),
     "mmif_ssim_loss_mode": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_ssim_terms": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
+    "mmif_ssim_loss_pad_workspace": (_sz, [_i32, _i32, _i32, _i32]),
+    "mmif_ssim_loss_pad": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "mmif_ssim_terms_pad": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
     "mmif_metric_moments_workspace": (_sz, [_i32] * 4),
     "mmif_metric_moments": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "mmif_metric_hist": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
