@@ -784,6 +784,24 @@ typedef struct {
 int mmif_conv2d_route(int32_t op, const mmif_tensor* a, const mmif_tensor* b, int32_t cin, int32_t cout, int32_t ksize, uint64_t mask_bits,
                       uint64_t accum_bits, int32_t fold, int32_t impl, int32_t num_cus, mmif_route* out);
 
+/* The same question for the image-side layers (csrc/image_route.hpp; their launches take kernel and grid from the function that answers
+ * here).  Pure host code: no device is touched.
+ *   op      the entry point (MMIF_IMAGE_OUT_BWD: mmif_conv2d_image_out_bwd)
+ *   dtype   of the blocked tensor the call is given: y (image_in_fwd), gy (image_in_wgrad), x (image_out_fwd / _wgrad / _bwd), gx (image_out_dgrad)
+ *   c       the layer's channels: cout of the image_in entries, cin of the image_out ones
+ *   cb, n, h, w, halo   channel blocks of that tensor's VIEW, its logical extent and its halo
+ * Returns 1 and fills *out, or 0 (the call would refuse this geometry; mmif_last_error says why).
+ *   name    "image_in_fwd<bf16,3>", "image_in_wgrad<f32,1>", "image_out_fwd16" (bf16, 16 channels, 3x3: persistent), "image_out_fwd_tiled<f32>"
+ *           (fp32, 16 channels, 3x3), "image_out_fwd<bf16,1>" (everything else), "image_out_dgrad<f32,3>", "image_out_wgrad<bf16,3>", "image_out_bwd16"
+ *   G       blocks launched per image / channel block: persistent kernels dim3(G); one-tile-per-block kernels dim3(tiles per image, n), G their
+ *           product; weight gradients dim3(G, cb), G = the partial sums per output that the reduce adds
+ *   tiles   tiles the blocks share out (image_out_dgrad: of gx's STORED domain); weight gradients: 256-pixel runs of the n h w pixels (more
+ *           than G: the blocks stride over them)
+ *   slices  of the weight gradients' reduce (else 0);  org: 0 */
+enum { MMIF_IMAGE_IN_FWD = 0, MMIF_IMAGE_IN_WGRAD = 1, MMIF_IMAGE_OUT_FWD = 2, MMIF_IMAGE_OUT_DGRAD = 3, MMIF_IMAGE_OUT_WGRAD = 4, MMIF_IMAGE_OUT_BWD = 5 };
+int mmif_conv2d_image_plan(int32_t op, int32_t dtype, int32_t c, int32_t ksize, int32_t cb, int32_t n, int32_t h, int32_t w, int32_t halo,
+                           mmif_route* out);
+
 /* mmif_dense_encoder_fwd: 2 (default) = the round-5 streaming kernel with 32-column strips, eight waves per CU; 1 = the
  * same with 64-column strips, four waves per CU (csrc/enc_stream2.hip: input-stationary accumulation; every stage within one bf16
  * rounding of its fp64 definition); 0 = the round-2 kernel (csrc/enc_stream.hip, bit-identical to the four layer-wise launches). */

@@ -3,11 +3,9 @@
 // ConvLayer(16,1,act=None) :86,131,179 / ConvLayer(64,1,ksize=1) :344.  Images are fp32 [n][h][w].
 // These layers are HBM-bound (K = 9 or M = 1): plain VALU kernels, fp32 math, T only on the
 // feature-map side.
-#include "wgrad_reduce.hpp"
+#include "image_route.hpp"
 
 namespace mmif {
-
-constexpr int ITILE = 16;
 
 __device__ inline float img_reflect(const float* img, int h, int w, int y, int x) {
     y = min(max(reflect_idx(y, h), 0), h - 1);
@@ -348,12 +346,10 @@ __global__ __launch_bounds__(256) void image_out_wgrad_kernel(TV tx, const float
     (void)npix;
 }
 
-constexpr int IMG_G = 512;
-
 }  // namespace mmif
 
 using namespace mmif;
-int image_out_fwd16_launch(const TV& tx, const float* w, const float* bias, float* img, int relu, hipStream_t st);   // image_bwd.hip
+int image_out_fwd16_launch(const ImagePlan& p, const TV& tx, const float* w, const float* bias, float* img, int relu, hipStream_t st);   // image_bwd.hip
 
 #define DISPATCH_T_KS(dtype, ks, CALL)                 \
     do {                                               \
@@ -363,6 +359,27 @@ int image_out_fwd16_launch(const TV& tx, const float* w, const float* bias, floa
             if ((ks) == 3) { CALL(bf16_t, 3); } else { CALL(bf16_t, 1); } \
         }                                              \
     } while (0)
+
+// the plan of an entry point's call (csrc/image_route.hpp): the launches below take kernel, tiles and G from it
+#define IMAGE_PLAN(p, what, op, t, c, ks)                                                                    \
+    const ImagePlan p = image_plan(op, (t)->dtype, c, ks, (t)->cb, (t)->n, (t)->h, (t)->w, (t)->halo);       \
+    MMIF_REQUIRE(p.kernel != ImagePlan::NONE, what ": %s", p.why)
+
+extern "C" int mmif_conv2d_image_plan(int32_t op, int32_t dtype, int32_t c, int32_t ksize, int32_t cb, int32_t n, int32_t h, int32_t w, int32_t halo,
+                                      mmif_route* out) {
+    if (out == nullptr) return 0;
+    memset(out, 0, sizeof(*out));
+    const ImagePlan p = image_plan(op, dtype, c, ksize, cb, n, h, w, halo);
+    if (p.kernel == ImagePlan::NONE) {
+        set_error("conv2d_image_plan: %s", p.why);
+        return 0;
+    }
+    image_plan_name(p, out->name, sizeof(out->name));
+    out->G = p.G;
+    out->tiles = (int32_t)(p.tiles < INT32_MAX ? p.tiles : INT32_MAX);      // (only a weight gradient's pixel runs can exceed it)
+    if (p.kernel == ImagePlan::IN_WGRAD || p.kernel == ImagePlan::OUT_WGRAD || p.kernel == ImagePlan::OUT_BWD16) out->slices = RED_SLICES;
+    return 1;
+}
 
 extern "C" size_t mmif_conv2d_image_wgrad_workspace(int32_t c, int32_t ksize) {
     return (size_t)IMG_G * cdiv(c, 16) * grouped_per(1, 16, ksize * ksize) * sizeof(float);   // (image_in_wgrad_reduce<ksize>::PER, the larger of the in / out layouts)
@@ -374,8 +391,9 @@ extern "C" int mmif_conv2d_image_in_fwd(const float* img, const float* w, const 
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "image_in_fwd: ksize must be 1 or 3");
     MMIF_REQUIRE(y->halo == 0 && cout <= y->cb * 8 && cout > 0, "image_in_fwd: bad output view");
     MMIF_REQUIRE(ksize == 1 || (y->h >= 2 && y->w >= 2), "reflect padding needs h,w >= 2");
+    IMAGE_PLAN(p, "image_in_fwd", MMIF_IMAGE_IN_FWD, y, cout, ksize);
     TV ty = make_tv(y);
-    const int tiles_x = cdiv(ty.w, ITILE), tiles_y = cdiv(ty.h, ITILE);
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
     const size_t shm = (size_t)(cout * ksize * ksize + cout) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
 #define CALL(T, KS) hipLaunchKernelGGL((image_in_fwd_kernel<T, KS>), dim3(tiles_x * tiles_y, ty.n), dim3(256), shm, st, img, ty, w, bias, cout, relu, tiles_x)
@@ -389,14 +407,14 @@ extern "C" int mmif_conv2d_image_in_wgrad(const float* img, const mmif_tensor* g
                                           void* stream) {
     if (int rc = validate_tensor(gy, "gy")) return rc;
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "image_in_wgrad: ksize must be 1 or 3");
+    IMAGE_PLAN(p, "image_in_wgrad", MMIF_IMAGE_IN_WGRAD, gy, cout, ksize);
     if (workspace_bytes < mmif_conv2d_image_wgrad_workspace(cout, ksize)) {
         set_error("image_in_wgrad: workspace too small");
         return MMIF_EWORKSPACE;
     }
     TV tg = make_tv(gy);
-    const long long npix = (long long)tg.n * tg.h * tg.w;
-    const int G = (int)(cdiv(npix, 256) < IMG_G ? cdiv(npix, 256) : IMG_G);
-    const int n_og = cdiv(cout, 16);
+    const long long npix = p.npix;
+    const int G = p.G, n_og = p.groups;
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
 #define CALL(T, KS) hipLaunchKernelGGL((image_in_wgrad_kernel<T, KS>), dim3(G, tg.cb), dim3(256), 0, st, img, tg, ws, cout, npix)
@@ -413,13 +431,14 @@ extern "C" int mmif_conv2d_image_out_fwd(const mmif_tensor* x, const float* w, c
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "image_out_fwd: ksize must be 1 or 3");
     MMIF_REQUIRE(x->halo == 0 && cin <= x->cb * 8 && cin > 0, "image_out_fwd: bad input view");
     MMIF_REQUIRE(ksize == 1 || (x->h >= 2 && x->w >= 2), "reflect padding needs h,w >= 2");
+    IMAGE_PLAN(p, "image_out_fwd", MMIF_IMAGE_OUT_FWD, x, cin, ksize);
     TV tx = make_tv(x);
-    const int tiles_x = cdiv(tx.w, ITILE), tiles_y = cdiv(tx.h, ITILE);
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
     const size_t shm = (size_t)cin * ksize * ksize * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (ksize == 3 && cin == 16 && x->cb == 2) {
-        // bf16: the persistent kernel of csrc/image_bwd.hip (round 6; 36 us against the tiled kernel's 40 at B = 32 256 x 256); fp32: the tiled kernel
-        if (x->dtype == MMIF_BF16) return image_out_fwd16_launch(tx, w, bias, img, relu, st);
+    // 3x3, 16 channels -- bf16: the persistent kernel of csrc/image_bwd.hip (round 6; 36 us against the tiled kernel's 40 at B = 32 256 x 256); fp32: the tiled kernel
+    if (p.kernel == ImagePlan::OUT_FWD16) return image_out_fwd16_launch(p, tx, w, bias, img, relu, st);
+    if (p.kernel == ImagePlan::OUT_FWD_TILED) {
         hipLaunchKernelGGL(image_out_fwd_tiled_kernel<float>, dim3(tiles_x * tiles_y, tx.n), dim3(256), 0, st, tx, w, bias, img, relu, tiles_x);
         return check_launch("image_out_fwd");
     }
@@ -436,6 +455,7 @@ extern "C" int mmif_conv2d_image_out_dgrad(const float* gimg, const float* y_img
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "image_out_dgrad: ksize must be 1 or 3");
     MMIF_REQUIRE(gx->halo >= ksize / 2, "image_out_dgrad: gx needs halo >= ksize/2");
     MMIF_REQUIRE(cin <= gx->cb * 8, "image_out_dgrad: gx view too small");
+    IMAGE_PLAN(p, "image_out_dgrad", MMIF_IMAGE_OUT_DGRAD, gx, cin, ksize);
     TV tgx = make_tv(gx);
     TV tm = tgx;
     if (mask_bits) {
@@ -445,7 +465,7 @@ extern "C" int mmif_conv2d_image_out_dgrad(const float* gimg, const float* y_img
                      "image_out_dgrad: x / gx mismatch");
         tm = make_tv(x);
     }
-    const int tiles_x = cdiv(tgx.ws, ITILE), tiles_y = cdiv(tgx.hs, ITILE);
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y;
     const size_t shm = (size_t)cin * ksize * ksize * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
 #define CALL(T, KS) hipLaunchKernelGGL((image_out_dgrad_kernel<T, KS>), dim3(tiles_x * tiles_y, tgx.n), dim3(256), shm, st, gimg, y_img, w, tm, tgx, cin, (unsigned long long)mask_bits, (unsigned long long)accum_bits, tiles_x)
@@ -460,14 +480,14 @@ extern "C" int mmif_conv2d_image_out_wgrad(const mmif_tensor* x, const float* gi
     if (int rc = validate_tensor(x, "x")) return rc;
     MMIF_REQUIRE(ksize == 1 || ksize == 3, "image_out_wgrad: ksize must be 1 or 3");
     MMIF_REQUIRE(x->halo == 0, "image_out_wgrad: x must be an activation (halo 0)");
+    IMAGE_PLAN(p, "image_out_wgrad", MMIF_IMAGE_OUT_WGRAD, x, cin, ksize);
     if (workspace_bytes < mmif_conv2d_image_wgrad_workspace(cin, ksize)) {
         set_error("image_out_wgrad: workspace too small");
         return MMIF_EWORKSPACE;
     }
     TV tx = make_tv(x);
-    const long long npix = (long long)tx.n * tx.h * tx.w;
-    const int G = (int)(cdiv(npix, 256) < IMG_G ? cdiv(npix, 256) : IMG_G);
-    const int n_cg = cdiv(cin, 16);
+    const long long npix = p.npix;
+    const int G = p.G, n_cg = p.groups;
     hipStream_t st = (hipStream_t)stream;
     float* ws = defer_ws((float*)workspace, (size_t)G * n_cg * grouped_per(16, 1, ksize * ksize) * sizeof(float));      // image_out_wgrad_reduce<ksize>::PER
 #define CALL(T, KS) hipLaunchKernelGGL((image_out_wgrad_kernel<T, KS>), dim3(G, tx.cb), dim3(256), 0, st, tx, gimg, y_img, ws, npix)

@@ -17,11 +17,11 @@
 // activation granule and g0 values requested before the current tile's arithmetic (one barrier per tile, double-buffered g0 tile),
 // weight-gradient accumulators in registers over all of a block's tiles, one partial per block reduced in fixed order by
 // image_out_wgrad_reduce (deterministic, no atomics).  HBM-bound by design: 67 MB of activations in, 67 MB of gradient out, 8 MB of image.
-#include "wgrad_reduce.hpp"
+#include "image_route.hpp"
 
 namespace mmif {
 
-constexpr int IB_TW = 32, IB_TH = 8;             // output tile: 8 rows x 32 columns = 256 pixels
+// (output tile: IB_TH x IB_TW = 8 rows x 32 columns = 256 pixels, csrc/image_route.hpp)
 // g0 tile: rows y0 - 2 .. y0 + TH + 2, columns x0 - 2 .. x0 + TW + 2 (a ring position looks one pixel beyond the ring: pp = H reads rows
 // H - 1 .. H + 1 and q = H - 2 may be the tile's last row)
 constexpr int IB_GW = IB_TW + 5, IB_GH = IB_TH + 5;
@@ -257,19 +257,13 @@ __global__ __launch_bounds__(512, 2) void image_out_fwd16_kernel(TV tx, const fl
 using namespace mmif;
 
 // (conv_image.hip's mmif_conv2d_image_out_fwd takes this kernel for bf16, 16 channels, 3x3)
-int image_out_fwd16_launch(const TV& tx, const float* w, const float* bias, float* img, int relu, hipStream_t st) {
-    const int tiles_x = cdiv(tx.w, IB_TW), tiles_y = cdiv(tx.h, IB_TH);
-    const long long total = (long long)tiles_x * tiles_y * tx.n;
-    if (total >= (1ll << 31)) { set_error("image_out_fwd: too many tiles"); return MMIF_EINVAL; }
-    int G = 1024;      // four persistent blocks per CU (39 registers, 25 KB of LDS each)
-    if (total < G) G = (int)total;
-    if (G >= 8) G = G / 8 * 8;
-    hipLaunchKernelGGL(image_out_fwd16_kernel, dim3(G), dim3(512), 0, st, tx, w, bias, img, relu, tiles_x, tiles_y, (int)total);
+int image_out_fwd16_launch(const ImagePlan& p, const TV& tx, const float* w, const float* bias, float* img, int relu, hipStream_t st) {
+    hipLaunchKernelGGL(image_out_fwd16_kernel, dim3(p.G), dim3(512), 0, st, tx, w, bias, img, relu, p.tiles_x, p.tiles_y, (int)p.tiles);
     return check_launch("image_out_fwd");
 }
 
 extern "C" int32_t mmif_conv2d_image_out_bwd_supported(int32_t dtype, int32_t cin, int32_t ksize, int32_t h, int32_t w) {
-    return dtype == MMIF_BF16 && cin == 16 && ksize == 3 && h >= 4 && w >= 4 ? 1 : 0;
+    return image_out_bwd16_shape(dtype, cin, ksize, h, w) ? 1 : 0;
 }
 
 extern "C" int mmif_conv2d_image_out_bwd(const mmif_tensor* x, const float* gimg, const float* y_img, const float* w, const mmif_tensor* gx,
@@ -284,13 +278,11 @@ extern "C" int mmif_conv2d_image_out_bwd(const mmif_tensor* x, const float* gimg
         set_error("image_out_bwd: workspace too small");
         return MMIF_EWORKSPACE;
     }
+    const ImagePlan p = image_plan(MMIF_IMAGE_OUT_BWD, x->dtype, cin, ksize, x->cb, x->n, x->h, x->w, x->halo);
+    MMIF_REQUIRE(p.kernel == ImagePlan::OUT_BWD16, "image_out_bwd: %s", p.why);
     TV tx = make_tv(x), tgx = make_tv(gx);
-    const int tiles_x = cdiv(tx.w, IB_TW), tiles_y = cdiv(tx.h, IB_TH);
-    const long long total = (long long)tiles_x * tiles_y * tx.n;
-    MMIF_REQUIRE(total < (1ll << 31), "image_out_bwd: too many tiles");
-    int G = 512;      // two persistent blocks per CU (512 = the workspace's block count, conv_image.hip IMG_G)
-    if (total < G) G = (int)total;
-    if (G >= 8) G = G / 8 * 8;
+    const int tiles_x = p.tiles_x, tiles_y = p.tiles_y, G = p.G;
+    const long long total = p.tiles;
     hipStream_t st = (hipStream_t)stream;
     float* ws = defer_ws((float*)workspace, (size_t)G * IB_PER * sizeof(float));
     hipLaunchKernelGGL(image_out_bwd16_kernel, dim3(G), dim3(512), 0, st, tx, tgx, gimg, y_img, w, ws, tiles_x, tiles_y, (int)total);

@@ -44,6 +44,7 @@ class MmifRoute(C.Structure):
 
 
 ROUTE_OPS = {"fwd": 0, "dgrad": 1, "dgrad_onto": 2, "dgrad_dup": 3, "wgrad": 4, "bwd_pair": 5, "bwd_wide": 6}
+IMAGE_OPS = {"in_fwd": 0, "in_wgrad": 1, "out_fwd": 2, "out_dgrad": 3, "out_wgrad": 4, "out_bwd": 5}      # mmif.h MMIF_IMAGE_*
 
 
 class MmifError(RuntimeError):
@@ -160,6 +161,7 @@ SIGNATURES = {
     "mmif_conv2d_image_out_dgrad": (_i32, [_vp, _vp, _vp, _TP, _TP, _i32, _i32, _u64, _u64, _vp]),
     "mmif_conv2d_image_out_wgrad": (_i32, [_TP, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "mmif_conv2d_image_wgrad_workspace": (_sz, [_i32, _i32]),
+    "mmif_conv2d_image_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(MmifRoute)]),
     "mmif_conv2d_image_out_bwd_supported": (_i32, [_i32, _i32, _i32, _i32, _i32]),
     "mmif_conv2d_image_out_bwd": (_i32, [_TP, _vp, _vp, _vp, _TP, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "mmif_fuse_elem_fwd": (_i32, [_TP, _TP, _TP, _i32, _vp]),

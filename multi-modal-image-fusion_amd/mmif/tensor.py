@@ -451,6 +451,16 @@ def image_wgrad_workspace_bytes(c, k):
     return lib.mmif_conv2d_image_wgrad_workspace(c, k)
 
 
+def image_plan(op, code, c, k, cb, n, h, w, halo=0):
+    """the kernel and grid of the image-side entry point `op` ('in_fwd', 'in_wgrad', 'out_fwd', 'out_dgrad', 'out_wgrad', 'out_bwd') on a view of
+    cb channel blocks of a [n, ., h, w] tensor of dtype code (mmif.h: mmif_conv2d_image_plan; no device is touched), or None where the call
+    would refuse"""
+    r = _lib.MmifRoute()
+    if not lib.mmif_conv2d_image_plan(_lib.IMAGE_OPS[op], code, c, k, cb, n, h, w, halo, r):
+        return None
+    return Route(r.name.decode(), r.G, r.slices, r.tiles, r.org)
+
+
 def maxpool_fwd(x, y):
     check(lib.mmif_maxpool2x2_fwd(x.d, y.d, stream_ptr()), "maxpool2x2_fwd")
 

@@ -243,6 +243,84 @@ def test_c_abi_validation_of_the_blocked_glue_entry_points_without_gpu():
     assert lib.mmif_nchw_to_blocked(f, 8, None, None) == -1 and lib.mmif_blocked_to_nchw(None, f, 8, None) == -1
 
 
+def test_c_abi_validation_of_the_image_layer_entry_points_without_gpu():
+    """csrc/conv_image.hip and csrc/image_bwd.hip (tests/image_cases.py defines everything these calls accept): every refusal comes before any
+    launch.  The two weight gradients refuse a view whose channel blocks do not match the channels' 16-channel groups -- their kernels lay the
+    partial sums out by the grid's channel blocks, the reduce and the workspace by the channels."""
+    from mmif._lib import MmifTensor, lib
+    buf = (ctypes.c_char * (1 << 16))()
+    base = ctypes.addressof(buf)
+    big = (ctypes.c_char * (1 << 20))()
+    ws, nws = ctypes.addressof(big), 1 << 20
+    f = (ctypes.c_float * 1024)()
+    r, err = ctypes.byref, lib.mmif_last_error
+
+    def t(h=8, w=8, halo=0, cb=2, dtype=1, flags=0):
+        return MmifTensor(base, dtype, 1, h, w, halo, cb, 0, cb, flags)
+    a, g1 = t(), t(halo=1)
+    for dtype in (0, 1):
+        assert lib.mmif_conv2d_image_wgrad_workspace(16, 3) <= nws
+        # ---- the weight gradients: channels against the view's blocks (a 16-channel call on a 3-block view would write partials past the workspace)
+        for c, cb in ((0, 2), (-8, 2), (17, 2), (33, 4), (24, 2), (40, 4), (64, 7), (8, 3), (16, 3), (16, 4)):
+            x = t(cb=cb, dtype=dtype)
+            assert lib.mmif_conv2d_image_in_wgrad(f, r(x), f, f, c, 3, 0, ws, nws, None) == -1, (c, cb)
+            assert b"image_in_wgrad: " in err(), err()
+            assert lib.mmif_conv2d_image_out_wgrad(r(x), f, None, f, f, c, 3, 0, ws, nws, None) == -1, (c, cb)
+            assert b"image_out_wgrad: " in err(), err()
+        assert b"16-channel groups" in err()
+        # ---- ksize
+        x, gx = t(dtype=dtype), t(halo=1, dtype=dtype)
+        for k in (0, 2, 5):
+            calls = [lib.mmif_conv2d_image_in_fwd(f, f, None, r(x), 16, k, 0, None),
+                     lib.mmif_conv2d_image_in_wgrad(f, r(x), f, f, 16, k, 0, ws, nws, None),
+                     lib.mmif_conv2d_image_out_fwd(r(x), f, None, f, 16, k, 0, None),
+                     lib.mmif_conv2d_image_out_dgrad(f, None, f, None, r(gx), 16, k, 0, 0, None),
+                     lib.mmif_conv2d_image_out_wgrad(r(x), f, None, f, f, 16, k, 0, ws, nws, None),
+                     lib.mmif_conv2d_image_out_bwd(r(x), f, None, f, r(gx), f, f, 16, k, 0, ws, nws, None)]
+            assert calls == [-1] * 6, (k, calls)
+            assert lib.mmif_conv2d_image_out_bwd_supported(dtype, 16, k, 8, 8) == 0
+        assert lib.mmif_conv2d_image_in_fwd(f, f, None, r(x), 16, 5, 0, None) == -1 and b"image_in_fwd: ksize must be 1 or 3" in err()
+        # ---- activations are halo 0; gx needs halo >= k / 2; masks need x
+        h1 = t(halo=1, dtype=dtype)
+        assert lib.mmif_conv2d_image_in_fwd(f, f, None, r(h1), 16, 3, 0, None) == -1 and b"image_in_fwd: bad output view" in err()
+        assert lib.mmif_conv2d_image_out_fwd(r(h1), f, None, f, 16, 3, 0, None) == -1 and b"image_out_fwd: bad input view" in err()
+        assert lib.mmif_conv2d_image_out_wgrad(r(h1), f, None, f, f, 16, 3, 0, ws, nws, None) == -1 and b"image_out_wgrad: x must be an activation" in err()
+        assert lib.mmif_conv2d_image_out_bwd(r(h1), f, None, f, r(gx), f, f, 16, 3, 0, ws, nws, None) == -1
+        assert lib.mmif_conv2d_image_out_bwd(r(x), f, None, f, r(x), f, f, 16, 3, 0, ws, nws, None) == -1        # gx without a halo
+        assert lib.mmif_conv2d_image_out_dgrad(f, None, f, None, r(x), 16, 3, 0, 0, None) == -1 and b"gx needs halo >= ksize/2" in err()
+        assert lib.mmif_conv2d_image_out_dgrad(f, None, f, None, r(gx), 16, 3, 1, 0, None) == -1 and b"mask_bits set but x is NULL" in err()
+        assert lib.mmif_conv2d_image_out_dgrad(f, None, f, r(h1), r(gx), 16, 3, 1, 0, None) == -1 and b"x / gx mismatch" in err()
+        assert lib.mmif_conv2d_image_out_dgrad(f, None, f, None, r(gx), 17, 3, 0, 0, None) == -1 and b"gx view too small" in err()
+        for c in (0, 17):
+            assert lib.mmif_conv2d_image_in_fwd(f, f, None, r(x), c, 3, 0, None) == -1 and lib.mmif_conv2d_image_out_fwd(r(x), f, None, f, c, 3, 0, None) == -1
+        # ---- reflect padding by 1 has no source below 2 x 2: all seven refuse at k = 3
+        for h, w in ((1, 8), (8, 1), (1, 1)):
+            x, gx = t(h, w, dtype=dtype), t(h, w, halo=1, dtype=dtype)
+            calls = [lib.mmif_conv2d_image_in_fwd(f, f, None, r(x), 16, 3, 0, None),
+                     lib.mmif_conv2d_image_in_wgrad(f, r(x), f, f, 16, 3, 0, ws, nws, None),
+                     lib.mmif_conv2d_image_out_fwd(r(x), f, None, f, 16, 3, 0, None),
+                     lib.mmif_conv2d_image_out_dgrad(f, None, f, None, r(gx), 16, 3, 0, 0, None),
+                     lib.mmif_conv2d_image_out_wgrad(r(x), f, None, f, f, 16, 3, 0, ws, nws, None),
+                     lib.mmif_conv2d_image_out_bwd(r(x), f, None, f, r(gx), f, f, 16, 3, 0, ws, nws, None)]
+            assert calls == [-1] * 6, (h, w, calls)
+            assert lib.mmif_conv2d_image_out_bwd_supported(dtype, 16, 3, h, w) == 0
+        assert lib.mmif_conv2d_image_out_wgrad(r(t(1, 8, dtype=dtype)), f, None, f, f, 16, 3, 0, ws, nws, None) == -1 and b"reflect padding needs h,w >= 2" in err()
+        # ---- a short workspace
+        x = t(dtype=dtype)
+        assert lib.mmif_conv2d_image_in_wgrad(f, r(x), f, f, 16, 3, 0, ws, 64, None) == -3 and b"image_in_wgrad: workspace too small" in err()
+        assert lib.mmif_conv2d_image_out_wgrad(r(x), f, None, f, f, 16, 3, 0, ws, 64, None) == -3 and b"image_out_wgrad: workspace too small" in err()
+        assert lib.mmif_conv2d_image_in_wgrad(f, r(x), f, f, 16, 1, 0, None, 0, None) == -3
+    assert lib.mmif_conv2d_image_out_bwd(r(a), f, None, f, r(g1), f, f, 16, 3, 0, ws, 64, None) == -3 and b"image_out_bwd: workspace too small" in err()
+    # ---- the fused backward: bf16, 16 channels, 3x3, h, w >= 4
+    assert lib.mmif_conv2d_image_out_bwd_supported(1, 16, 3, 4, 4) == 1 and lib.mmif_conv2d_image_out_bwd_supported(1, 16, 3, 256, 256) == 1
+    for args in ((0, 16, 3, 8, 8), (1, 8, 3, 8, 8), (1, 24, 3, 8, 8), (1, 16, 1, 8, 8), (1, 16, 3, 3, 8), (1, 16, 3, 8, 3)):
+        assert lib.mmif_conv2d_image_out_bwd_supported(*args) == 0, args
+    assert lib.mmif_conv2d_image_out_bwd(r(t(dtype=0)), f, None, f, r(t(halo=1, dtype=0)), f, f, 16, 3, 0, ws, nws, None) == -1 and b"image_out_bwd: bf16" in err()
+    assert lib.mmif_conv2d_image_out_bwd(r(t(3, 8)), f, None, f, r(t(3, 8, halo=1)), f, f, 16, 3, 0, ws, nws, None) == -1
+    assert lib.mmif_conv2d_image_out_bwd(r(t(cb=3)), f, None, f, r(t(halo=1, cb=3)), f, f, 16, 3, 0, ws, nws, None) == -1
+    assert lib.mmif_conv2d_image_out_bwd(r(a), f, None, f, r(t(8, 9, halo=1)), f, f, 16, 3, 0, ws, nws, None) == -1
+
+
 def test_c_abi_validation_of_the_norm_and_optimiser_entry_points_without_gpu():
     """csrc/norm.hip's nine entry points and mmif_clip_adam_step (tests/norm_cases.py and tests/optim_cases.py define everything these calls
     accept): every refusal comes before any launch, with its return code and message.  None of these calls may ever reach a device."""
