@@ -569,6 +569,26 @@ int mmif_metric_vif(const float* a, const float* b, const float* f, int32_t n, i
 size_t mmif_metric_msssim_workspace(int32_t n, int32_t h, int32_t w);
 int mmif_metric_msssim(const float* a, const float* b, const float* f, int32_t n, int32_t h, int32_t w, float data_range, float* out,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* calc_ssim (:316-364) for every window and map form (csrc/metric_ssim.hip): k = min(win_size, h, w) <= 11, even k included, sigma
+ * 1.5; use_padding != 0 reflect-pads every window pass by p = k / 2 (torch 'reflect').  The maps are Hm x Wm = (h + 2p - k + 1) x
+ * (w + 2p - k + 1), p = 0 without padding (so h x w for odd and (h + 1) x (w + 1) for even padded k).  Outputs, each optional (at least
+ * one): ssim_map, cs_map fp32 [n][Hm][Wm]; sums fp64 [n][2] = sum of the ssim map, sum of the cs map of each sample (fp64 arithmetic,
+ * fixed order: bit-identical whatever batch the sample is in).  The workspace is only read when sums != NULL.
+ * MMIF_EINVAL: NULL image, n < 1, win_size < 1, k > 11, no output. */
+size_t mmif_metric_ssim_maps_workspace(int32_t n, int32_t h, int32_t w, int32_t win_size, int32_t use_padding);
+int mmif_metric_ssim_maps(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, int32_t use_padding,
+                          double data_range, float* ssim_map, float* cs_map, double* sums, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* calc_msssim (:368-403) for every window, with or without padding, from 9x9 up: out[2][6][n] fp64 in the layout of
+ * mmif_metric_msssim (pair p = (a, f) | (b, f): cs means of levels 0..3, ssim mean of level 4, slot 5 = level-0 ssim mean; b may be
+ * NULL: pair 2 = pair 1).  The window of level l is min(win_size, h_l, w_l) <= 11.  Below 9 px level 3 is 1 px wide and its reflect
+ * pad is undefined (the reference raises): MMIF_EINVAL. */
+size_t mmif_metric_msssim_any_workspace(int32_t n, int32_t h, int32_t w);
+int mmif_metric_msssim_any(const float* a, const float* b, const float* f, int32_t n, int32_t h, int32_t w, int32_t win_size,
+                           int32_t use_padding, double data_range, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* HOST only: the window of the two calls above, as the reference's create_window(win_size, 1.5) builds it: taps[win_size] (fp32 taps
+ * divided by their fp32 sum) and window[win_size][win_size] (fp32 products of two taps).  win_size 1..11. */
+int mmif_metric_ssim_window(int32_t win_size, float* taps, float* window);
 /* TVLoss core/loss.py:347-358 = NormLoss(l1|l2)(x[1:] - x[:-1]) + NormLoss(x[:, 1:] - x[:, :-1]) over n images [h][w]. */
 size_t mmif_tv_loss_workspace(void);
 int mmif_tv_loss(const float* x, int32_t n, int32_t h, int32_t w, float weight, int32_t l2, float* loss_out, float* grad_out,

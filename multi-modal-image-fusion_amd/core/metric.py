@@ -2,14 +2,20 @@
 """Evaluation metrics -- API mirror of the reference's core/metric.py (the 17 names of its __all__) plus `fusion_metrics`, the
 per-sample table of eval.py:29-76.
 
-`calc_ssim` is the SSIM that test.py:49-52 prints per fused image: it shares its maths with SSIMLoss (11x11 Gaussian window, valid
-correlation) and runs on the same fused HIP kernel (csrc/loss.hip: separable window through LDS, block sums, fixed-order second
-stage).  The other metrics run on csrc/metric.hip (moments, histograms, entropies, Qabf, VIF) and on mmif_metric_msssim (the loss's
-SSIM kernels and pyramid): every kernel emits PER-SAMPLE raw terms (sums, counts), finished here in fp64 into
+`calc_ssim` in the configuration test.py:49-52 prints per fused image (11x11 window, valid correlation, scalar mean, images of at
+least 11 px) shares its maths with SSIMLoss and runs on the same fused HIP kernel (csrc/loss_modes.hip: separable window through LDS,
+block sums, fixed-order second stage).  Every other calc_ssim call on CUDA tensors -- any win_size with min(win_size, h, w) <= 11 (even
+and shrunk windows included), use_padding=True, size_average=False, full=True -- runs on mmif_metric_ssim_maps (csrc/metric_ssim.hip:
+run-time window, reflect padding in the tile loader, fp64 arithmetic, optional ssim / cs maps and fp64 per-sample sums).
+`calc_msssim` keeps mmif_metric_msssim (the loss's SSIM kernels and pyramid) for win_size 11 without padding from 161 px up; every other
+CUDA call on images of at least 9x9 runs on mmif_metric_msssim_any (the same window kernel on an fp64 pyramid), and so does the
+ssim / msssim pair of `fusion_metrics` below 161 px, in one call for the whole batch.  The other metrics run on csrc/metric.hip (moments,
+histograms, entropies, Qabf, VIF).  Every kernel emits PER-SAMPLE raw terms (sums, counts), finished here in fp64 into
   * the reference's value for a [B,1,H,W] batch -- for B > 1 the POOLED value (e.g. the entropy of the summed histogram), and
   * `fusion_metrics`: one value per sample.
-Values are 0-dim fp64 device tensors.  Argument combinations the kernels do not cover (use_padding=True, win_size != 11, MS-SSIM
-below 161 px) run as stock torch ops (core/_stock.py).
+Values are 0-dim fp64 device tensors (calc_ssim: fp32, as the stock composition returned).  What stays on stock torch ops
+(core/_stock.py), errors included: calc_ssim / calc_msssim on CPU tensors, windows above 11, and MS-SSIM below 9 px (where the
+reference itself raises: level 3 is 1 px wide).
 """
 import ctypes as C
 from math import exp
@@ -28,9 +34,10 @@ __all__ = [
 
 
 def calc_ssim(img1, img2, win_size=11, data_range=255.0, use_padding=False, size_average=True, full=False):
-    """Mean SSIM of two single-channel image batches [B,1,H,W] (reference default data_range=255; test.py passes 1.0).
-    Returns a 0-dim tensor.  The accelerated configuration is the one test.py uses; every other argument combination runs as stock
-    torch ops with the reference's results (core/_stock.py)."""
+    """SSIM of two single-channel image batches [B,1,H,W] (reference default data_range=255; test.py passes 1.0): the mean over the
+    whole batch as a 0-dim tensor, or with size_average=False the per-pixel map [B,1,Hm,Wm]; full=True returns the pair (ssim, cs).
+    The window is min(win_size, h, w) taps wide.  test.py's configuration runs on mmif_ssim_terms, every other call on CUDA tensors
+    with a window of at most 11 on mmif_metric_ssim_maps; CPU tensors and larger windows run as stock torch ops (core/_stock.py)."""
     if img1.shape != img2.shape:
         raise ValueError("img1 and img2 must have the same shape")
     if img1.dim() != 4 or img1.shape[1] != 1:
@@ -38,8 +45,16 @@ def calc_ssim(img1, img2, win_size=11, data_range=255.0, use_padding=False, size
         raise RuntimeError(f"calc_ssim takes single-channel images [B,1,H,W]; got {tuple(img1.shape)}")
     n, _, h, w = img1.shape
     if win_size != 11 or min(h, w) < 11 or use_padding or not size_average or full:
-        from . import _stock
-        return _stock.metric_ssim(img1.float(), img2.float(), win_size, data_range, use_padding, size_average, full)
+        if not (img1.is_cuda and img2.is_cuda) or win_size < 1 or min(win_size, h, w) > 11 or min(n, h, w) < 1:
+            from . import _stock
+            return _stock.metric_ssim(img1.float(), img2.float(), win_size, data_range, use_padding, size_average, full)
+        a, b = _images(img1, img2, min_size=1, what='calc_ssim')
+        if size_average:
+            sums, hm, wm = _ssim_maps(a, b, win_size, use_padding, data_range, maps=False)
+            ssim, cs = (sums.sum(0) / (n * hm * wm)).float()
+        else:
+            ssim, cs = _ssim_maps(a, b, win_size, use_padding, data_range, maps=True, cs=full)
+        return (ssim, cs) if full else ssim
     T.require_device(img1, "img1")
     T.require_device(img2, "img2")
     a = img1.detach().contiguous().float()
@@ -57,7 +72,8 @@ def calc_ssim(img1, img2, win_size=11, data_range=255.0, use_padding=False, size
 # ------------------------------------------------------------------ input handling and the per-sample kernels
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 VIF_MIN = 41        # scale-4 map needs 3 px: 3 <- 7 <- 17 <- 41 through the valid filters and the [::2, ::2] decimations
-MSSSIM_MIN = 161    # the HIP MS-SSIM keeps the 11x11 window down to level 4
+MSSSIM_MIN = 161    # mmif_metric_msssim keeps the 11x11 window down to level 4
+MSSSIM_ANY_MIN = 9  # mmif_metric_msssim_any: level 3 of a smaller image is 1 px wide and cannot be reflect-padded (the reference raises)
 
 
 def _p(t):
@@ -177,6 +193,36 @@ def _msssim_terms(a, b, f, data_range):
     ws = _workspace(lib.mmif_metric_msssim_workspace(n, h, w), a.device)
     check(lib.mmif_metric_msssim(_p(a), _p(b) if b is not None else None, _p(f), n, h, w, float(data_range), _p(out), _p(ws), ws.numel(),
                                  T.stream_ptr()), "metric_msssim")
+    return out
+
+
+def _ssim_maps(a, b, win_size, use_padding, data_range, maps, cs=True):
+    """mmif_metric_ssim_maps on fp32 [n,1,h,w] images: maps=False -> (fp64 sums [n, 2] = sum ssim, sum cs of each sample, Hm, Wm);
+    maps=True -> (ssim map, cs map | None) fp32 [n,1,Hm,Wm]"""
+    n, _, h, w = a.shape
+    k = min(win_size, h, w)
+    p = k // 2 if use_padding else 0
+    hm, wm = h + 2 * p - k + 1, w + 2 * p - k + 1
+    if maps:
+        sm = torch.empty((n, 1, hm, wm), dtype=torch.float32, device=a.device)
+        cm = torch.empty_like(sm) if cs else None
+        check(lib.mmif_metric_ssim_maps(_p(a), _p(b), n, h, w, int(win_size), int(bool(use_padding)), float(data_range), _p(sm),
+                                        _p(cm) if cs else None, None, None, 0, T.stream_ptr()), "metric_ssim_maps")
+        return sm, cm
+    sums = torch.empty((n, 2), dtype=torch.float64, device=a.device)
+    ws = _workspace(lib.mmif_metric_ssim_maps_workspace(n, h, w, int(win_size), int(bool(use_padding))), a.device)
+    check(lib.mmif_metric_ssim_maps(_p(a), _p(b), n, h, w, int(win_size), int(bool(use_padding)), float(data_range), None, None, _p(sums),
+                                    _p(ws), ws.numel(), T.stream_ptr()), "metric_ssim_maps")
+    return sums, hm, wm
+
+
+def _msssim_any(a, b, f, win_size, use_padding, data_range):
+    """[2,6,n] fp64 in the layout of _msssim_terms, for any window up to 11, padded or not, images from 9x9 (mmif_metric_msssim_any)"""
+    n, _, h, w = a.shape
+    out = torch.empty((2, 6, n), dtype=torch.float64, device=a.device)
+    ws = _workspace(lib.mmif_metric_msssim_any_workspace(n, h, w), a.device)
+    check(lib.mmif_metric_msssim_any(_p(a), _p(b) if b is not None else None, _p(f), n, h, w, int(win_size), int(bool(use_padding)),
+                                     float(data_range), _p(out), _p(ws), ws.numel(), T.stream_ptr()), "metric_msssim_any")
     return out
 
 
@@ -314,14 +360,18 @@ def calc_Labf(img1, img2, imgf, L=1.5):
 
 
 def calc_msssim(img1, img2, win_size=11, data_range=255.0, use_padding=False):
-    """MS-SSIM of two batches (pooled means per level).  The HIP path covers win_size 11 without padding on images >= 161 px;
-    everything else runs as stock torch ops."""
+    """MS-SSIM of two batches (pooled means per level).  win_size 11 without padding on images >= 161 px runs on mmif_metric_msssim;
+    every other call on CUDA tensors of at least 9x9 with a window of at most 11 on mmif_metric_msssim_any; the rest (CPU tensors,
+    larger windows, images below 9 px, where the reference raises) as stock torch ops."""
     if img1.dim() != 4 or img1.shape[1] != 1 or img1.shape != img2.shape:
         raise RuntimeError(f"calc_msssim takes two single-channel batches [B,1,H,W] of one shape; got {tuple(img1.shape)}, {tuple(img2.shape)}")
-    h, w = img1.shape[-2:]
+    n, _, h, w = img1.shape
     if win_size != 11 or use_padding or min(h, w) < MSSSIM_MIN:
-        from . import _stock
-        return _stock.metric_msssim(img1.double(), img2.double(), win_size, data_range, use_padding)
+        if not (img1.is_cuda and img2.is_cuda) or win_size < 1 or min(win_size, h, w) > 11 or min(h, w) < MSSSIM_ANY_MIN or n < 1:
+            from . import _stock
+            return _stock.metric_msssim(img1.double(), img2.double(), win_size, data_range, use_padding)
+        a, b = _images(img1, img2, what='calc_msssim')
+        return _ms_combine(_msssim_any(a, None, b, win_size, use_padding, data_range)[0, :5].mean(1))
     a, b = _images(img1, img2, what='calc_msssim')
     v = _msssim_terms(a, None, b, data_range)[0, :5].double().mean(1)
     return _ms_combine(v)
@@ -340,7 +390,7 @@ FUSION_METRICS = ('sd', 'ag', 'sf', 'mse', 'psnr', 'cc', 'scd', 'en', 'ce', 'mi'
 def fusion_metrics(img1, img2, imgf):
     """The 16 values of the reference's eval_metrics (eval.py:29-76) for every sample of a [B,1,H,W] triple (sources img1, img2,
     fused imgf, 0..255 values): a dict of [B] fp64 device tensors.  One call per kernel family for the whole batch, no host sync.
-    Images of at least 41x41 (VIF); below 161 px MS-SSIM runs as stock torch ops per sample."""
+    Images of at least 41x41 (VIF); below 161 px ssim and msssim come from one mmif_metric_msssim_any call."""
     a, b, f = _images(img1, img2, imgf, min_size=VIF_MIN, what='fusion_metrics')
     n, _, h, w = a.shape
     npix = h * w
@@ -363,16 +413,9 @@ def fusion_metrics(img1, img2, imgf):
     r['qabf'], r['nabf'], r['labf'] = q[:, 0] / q[:, 1], q[:, 2] / q[:, 1], q[:, 3] / q[:, 1]
     if min(h, w) >= MSSSIM_MIN:
         ms = _msssim_terms(a, b, f, 255.0).double()
-        r['ssim'] = (ms[0, 5] + ms[1, 5]) * 0.5
-        r['msssim'] = (_ms_combine(ms[0, :5]) + _ms_combine(ms[1, :5])) * 0.5
     else:
-        from . import _stock
-        ws = _workspace(lib.mmif_ssim_loss_mode_workspace(2 * n, h, w, 1), a.device)
-        s = torch.empty((3, 2 * n), dtype=torch.float32, device=a.device)
-        ab, ff = torch.cat([a, b]), torch.cat([f, f])   # held until the launch is enqueued
-        check(lib.mmif_ssim_terms(_p(ab), _p(ff), 2 * n, h, w, 11, 255.0, _p(s), _p(ws), ws.numel(), T.stream_ptr()), "fusion_metrics ssim")
-        r['ssim'] = (s[0, :n].double() + s[0, n:].double()) * 0.5
-        r['msssim'] = torch.stack([(_stock.metric_msssim(a[i:i + 1].double(), f[i:i + 1].double())
-                                    + _stock.metric_msssim(b[i:i + 1].double(), f[i:i + 1].double())) * 0.5 for i in range(n)])
+        ms = _msssim_any(a, b, f, 11, False, 255.0)
+    r['ssim'] = (ms[0, 5] + ms[1, 5]) * 0.5
+    r['msssim'] = (_ms_combine(ms[0, :5]) + _ms_combine(ms[1, :5])) * 0.5
     r['viff'] = _viff_value(_vif(a, b, f), False)
     return {k: r[k] for k in FUSION_METRICS}

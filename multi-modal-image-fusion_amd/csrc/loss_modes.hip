@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "ssim_pool.hpp"
 
 namespace mmif {
 
@@ -293,18 +294,8 @@ __global__ void value_finish_kernel(const float* __restrict__ sums, int n, float
 }
 
 // ------------------------------------------------------------------ ms-ssim pyramid
-// dst[y][x] = mean of the 2x2 cell of the source reflect-padded to even size (core/loss.py:146-153)
-__global__ void avg_pool_pad_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int h, int w) {
-    const int ho = (h + 1) / 2, wo = (w + 1) / 2;
-    const long long total = (long long)n * ho * wo;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int x = i % wo, y = (i / wo) % ho, b = i / ((long long)wo * ho);
-        const float* p = src + (long long)b * h * w;
-        const int y0 = 2 * y, y1 = (2 * y + 1 < h) ? 2 * y + 1 : h - 2, x0 = 2 * x, x1 = (2 * x + 1 < w) ? 2 * x + 1 : w - 2;
-        dst[i] = 0.25f * ((p[(long long)y0 * w + x0] + p[(long long)y0 * w + x1]) + (p[(long long)y1 * w + x0] + p[(long long)y1 * w + x1]));
-    }
-}
-// adjoint, accumulated into the finer level's gradient
+// forward step: avg_pool_pad_kernel<float> of ssim_pool.hpp (shared with the metric side); its adjoint, accumulated into the finer
+// level's gradient
 __global__ void avg_pool_pad_bwd_kernel(const float* __restrict__ gc, float* __restrict__ gf, int n, int h, int w) {
     const int ho = (h + 1) / 2, wo = (w + 1) / 2;
     const long long total = (long long)n * h * w;
@@ -516,9 +507,9 @@ static int ssim_modes_run(const float* img1, const float* img2, const float* img
         lg[l] = pf + sz;
         pyr = lg[l] + sz;
         const int grid = ew_grid((long long)sz);
-        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, lx1[l - 1], p1, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, lx2[l - 1], p2, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, lf[l - 1], pf, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lx1[l - 1], p1, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lx2[l - 1], p2, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lf[l - 1], pf, n, hs[l - 1], wsz[l - 1]);
         if (int rc = check_launch("avg_pool_pad")) return rc;
         lx1[l] = p1;
         lx2[l] = p2;
@@ -707,9 +698,9 @@ extern "C" int mmif_metric_msssim(const float* a, const float* b, const float* f
         float* pf = pb + sz;
         pyr = pf + sz + 64;
         const int grid = ew_grid((long long)sz);
-        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, la[l - 1], pa, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, lb[l - 1], pb, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel, dim3(grid), dim3(256), 0, st, lf[l - 1], pf, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, la[l - 1], pa, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lb[l - 1], pb, n, hs[l - 1], wsz[l - 1]);
+        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lf[l - 1], pf, n, hs[l - 1], wsz[l - 1]);
         if (int rc = check_launch("metric_msssim pool")) return rc;
         la[l] = pa;
         lb[l] = pb;

@@ -219,6 +219,11 @@ SIGNATURES = {
     "mmif_metric_vif": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_metric_msssim_workspace": (_sz, [_i32] * 3),
     "mmif_metric_msssim": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
+    "mmif_metric_ssim_maps_workspace": (_sz, [_i32] * 5),
+    "mmif_metric_ssim_maps": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmif_metric_msssim_any_workspace": (_sz, [_i32] * 3),
+    "mmif_metric_msssim_any": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
+    "mmif_metric_ssim_window": (_i32, [_i32, _vp, _vp]),
     "mmif_tv_loss_workspace": (_sz, []),
     "mmif_tv_loss": (_i32, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_pixel_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
