@@ -535,6 +535,26 @@ int mmif_ssim_loss_pad(const float* img1, const float* img2, const float* imgf, 
  * h, w >= win_size -> out[3][n].  Values only; workspace as mmif_ssim_loss_pad_workspace(n, h, w, 1). */
 int mmif_ssim_terms_pad(const float* img1, const float* img2, int32_t n, int32_t h, int32_t w, int32_t win_size, float data_range,
                         float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* TVLoss core/loss.py:347-358 = NormLoss(l1|l2)(x[1:] - x[:-1]) + NormLoss(x[:, 1:] - x[:, :-1]) over n images [h][w]. */
+size_t mmif_tv_loss_workspace(void);
+int mmif_tv_loss(const float* x, int32_t n, int32_t h, int32_t w, float weight, int32_t l2, float* loss_out, float* grad_out,
+                 void* workspace, size_t workspace_bytes, void* stream);
+/* PixelLoss core/loss.py:287-304 (NormLoss 'l1'|'l2' :361-385); mode 0 = 'avg', 1 = 'max'. */
+int mmif_pixel_loss(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w,
+                    float weight, int32_t mode_max, int32_t l2, float* loss_out, float* grad_out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* GradLoss core/loss.py:307-344: Sobel |gx|+|gy| on the reflect-padded image. */
+int mmif_grad_loss(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w,
+                   float weight, int32_t mode_max, int32_t l2, float* loss_out, float* grad_out, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* The three loss terms of the reference's train step (train.py:64-69: SSIMLoss('ssim') + PixelLoss + GradLoss, their sum, the three
+ * d/dimgf contributions autograd adds up) as ONE call: the kernels of the three entry points above, the pixel and Sobel kernels adding
+ * onto the SSIM term's gradient, one finish kernel.  loss_out = {l1 + l2 + l3, l1, l2, l3, total again} (5 floats on the device); grad_out (or NULL)
+ * = d(total)/d(imgf).  Weights as the modules' `weight`; *_max = mode 'max' (else 'avg'); *_l2 = mode 'l2' (else 'l1'). */
+size_t mmif_fusion_loss_workspace(int32_t n, int32_t h, int32_t w);
+int mmif_fusion_loss(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float w_ssim,
+                     float data_range, float w_pixel, int32_t pixel_max, int32_t pixel_l2, float w_grad, int32_t grad_max,
+                     int32_t grad_l2, float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- Fusion-quality metrics of eval.py (core/metric.py:1-491): per-SAMPLE raw terms of fp32 [n][h][w] images holding 0..255
  * values; the per-image and pooled values are finished from them on the host side (core/metric.py of this package).  fp64 block
  * partials + fixed-order second stages: a sample's terms are bit-identical whatever batch it is in.
@@ -589,26 +609,6 @@ int mmif_metric_msssim_any(const float* a, const float* b, const float* f, int32
 /* HOST only: the window of the two calls above, as the reference's create_window(win_size, 1.5) builds it: taps[win_size] (fp32 taps
  * divided by their fp32 sum) and window[win_size][win_size] (fp32 products of two taps).  win_size 1..11. */
 int mmif_metric_ssim_window(int32_t win_size, float* taps, float* window);
-/* TVLoss core/loss.py:347-358 = NormLoss(l1|l2)(x[1:] - x[:-1]) + NormLoss(x[:, 1:] - x[:, :-1]) over n images [h][w]. */
-size_t mmif_tv_loss_workspace(void);
-int mmif_tv_loss(const float* x, int32_t n, int32_t h, int32_t w, float weight, int32_t l2, float* loss_out, float* grad_out,
-                 void* workspace, size_t workspace_bytes, void* stream);
-/* PixelLoss core/loss.py:287-304 (NormLoss 'l1'|'l2' :361-385); mode 0 = 'avg', 1 = 'max'. */
-int mmif_pixel_loss(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w,
-                    float weight, int32_t mode_max, int32_t l2, float* loss_out, float* grad_out, void* workspace,
-                    size_t workspace_bytes, void* stream);
-/* GradLoss core/loss.py:307-344: Sobel |gx|+|gy| on the reflect-padded image. */
-int mmif_grad_loss(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w,
-                   float weight, int32_t mode_max, int32_t l2, float* loss_out, float* grad_out, void* workspace,
-                   size_t workspace_bytes, void* stream);
-/* The three loss terms of the reference's train step (train.py:64-69: SSIMLoss('ssim') + PixelLoss + GradLoss, their sum, the three
- * d/dimgf contributions autograd adds up) as ONE call: the kernels of the three entry points above, the pixel and Sobel kernels adding
- * onto the SSIM term's gradient, one finish kernel.  loss_out = {l1 + l2 + l3, l1, l2, l3, total again} (5 floats on the device); grad_out (or NULL)
- * = d(total)/d(imgf).  Weights as the modules' `weight`; *_max = mode 'max' (else 'avg'); *_l2 = mode 'l2' (else 'l1'). */
-size_t mmif_fusion_loss_workspace(int32_t n, int32_t h, int32_t w);
-int mmif_fusion_loss(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float w_ssim,
-                     float data_range, float w_pixel, int32_t pixel_max, int32_t pixel_l2, float w_grad, int32_t grad_max,
-                     int32_t grad_l2, float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Backward of ONE thin 3x3 ConvLayer (64 -> 32, 32 -> 16: decode.2 / decode.3 of every PFNet / DenseFuse decoder, core/model.py:83-85) in one
  * launch: gx = [x > 0] * dgrad(gy) in the folded convention -- what mmif_conv2d_reflect_dgrad_folded(mask_bits = all, accum_bits = 0)

@@ -69,35 +69,13 @@ class _LossFn(torch.autograd.Function):
         return ctx.grad * g, None, None, None, None, None, None
 
 
-_SSIM_MODES = {'w-ssim': 1, 'ms-ssim': 2, 'msw-ssim': 3}
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class _ModeLossFn(torch.autograd.Function):
-    """SSIMLoss 'w-ssim' | 'ms-ssim' | 'msw-ssim' (reference core/loss.py:259-277) on csrc/loss_modes.hip."""
-
-    @staticmethod
-    def forward(ctx, imgf, img1, img2, mode, weight, data_range):
-        i1, i2, f = _prep(img1, img2, imgf)
-        n, _, h, w = f.shape
-        need = ctx.needs_input_grad[0]
-        out = torch.empty(1, dtype=torch.float32, device=f.device)
-        grad = torch.empty_like(f) if need else None
-        nbytes = lib.mmif_ssim_loss_mode_workspace(n, h, w, mode)
-        ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=f.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        check(lib.mmif_ssim_loss_mode(p(i1), p(i2), p(f), n, h, w, weight, data_range, mode, p(out), p(grad), p(ws), ws.numel() * 4,
-                                      T.stream_ptr()), "ssim_loss_mode")
-        ctx.grad = grad
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.grad is None:
-            return (None,) * 6
-        return ctx.grad * g, None, None, None, None, None
-
-
-_PAD_MODES = {'ssim': 0, 'w-ssim': 1, 'ms-ssim': 2, 'msw-ssim': 3}
+_SSIM_MODES = {'w-ssim': 1, 'ms-ssim': 2, 'msw-ssim': 3}                   # mode argument of mmif_ssim_loss_mode ('ssim': mmif_ssim_loss)
+_PAD_MODES = {'ssim': 0, 'w-ssim': 1, 'ms-ssim': 2, 'msw-ssim': 3}         # mode argument of mmif_ssim_loss_pad
+_UNPADDED, _PADDED = 'ssim_loss_mode', 'ssim_loss_pad'                     # the two entry points of _SsimLossFn
 
 
 def _pad_limit(mode):
@@ -114,30 +92,42 @@ def _pad_on_device(limit, *imgs):
     return min(x.shape[-2:]) >= limit
 
 
-class _PadLossFn(torch.autograd.Function):
-    """SSIMLoss(mode, use_padding=True) (reference core/loss.py:42-49, :252-284) on the reflect-padded kernels of csrc/loss_modes.hip;
-    mode: 0 'ssim' | 1 'w-ssim' | 2 'ms-ssim' | 3 'msw-ssim'."""
+class _SsimLossFn(torch.autograd.Function):
+    """The SSIMLoss modes on csrc/loss_modes.hip through one of its two entry points (each with its `<entry>_workspace` query):
+    _UNPADDED  mmif_ssim_loss_mode: 'w-ssim' | 'ms-ssim' | 'msw-ssim' (reference core/loss.py:259-277), mode from _SSIM_MODES
+    _PADDED    mmif_ssim_loss_pad: SSIMLoss(mode, use_padding=True) on the reflect-padded kernels (reference core/loss.py:42-49,
+               :252-284), mode from _PAD_MODES."""
 
     @staticmethod
-    def forward(ctx, imgf, img1, img2, mode, weight, data_range):
+    def forward(ctx, imgf, img1, img2, entry, mode, weight, data_range):
         i1, i2, f = _prep(img1, img2, imgf)
         n, _, h, w = f.shape
         need = ctx.needs_input_grad[0]
         out = torch.empty(1, dtype=torch.float32, device=f.device)
         grad = torch.empty_like(f) if need else None
-        nbytes = lib.mmif_ssim_loss_pad_workspace(n, h, w, mode)
+        nbytes = getattr(lib, f"mmif_{entry}_workspace")(n, h, w, mode)
         ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=f.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        check(lib.mmif_ssim_loss_pad(p(i1), p(i2), p(f), n, h, w, weight, data_range, mode, p(out), p(grad), p(ws), ws.numel() * 4,
-                                     T.stream_ptr()), "ssim_loss_pad")
+        check(getattr(lib, f"mmif_{entry}")(_p(i1), _p(i2), _p(f), n, h, w, weight, data_range, mode, _p(out), _p(grad), _p(ws), ws.numel() * 4,
+                                            T.stream_ptr()), entry)
         ctx.grad = grad
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
         if ctx.grad is None:
-            return (None,) * 6
-        return ctx.grad * g, None, None, None, None, None
+            return (None,) * 7
+        return ctx.grad * g, None, None, None, None, None, None
+
+
+def ssim_terms(i1, i2, win_size, data_range, pad):
+    """[3, n] fp32: the per-sample means of the ssim map, the cs map and the clamped variance sigma of i1, for contiguous fp32 device
+    images [n,1,h,w] and a window of 3 / 5 / 7 / 9 / 11 taps (mmif_ssim_terms; pad: the reflect-padded mmif_ssim_terms_pad)"""
+    n, _, h, w = i1.shape
+    out = torch.empty((3, n), dtype=torch.float32, device=i1.device)
+    ws = torch.empty(lib.mmif_ssim_loss_mode_workspace(n, h, w, 1) // 4 + 1, dtype=torch.float32, device=i1.device)
+    entry = "ssim_terms_pad" if pad else "ssim_terms"
+    check(getattr(lib, "mmif_" + entry)(_p(i1), _p(i2), n, h, w, win_size, float(data_range), _p(out), _p(ws), ws.numel() * 4, T.stream_ptr()), entry)
+    return out
 
 
 class _TVFn(torch.autograd.Function):
@@ -153,8 +143,7 @@ class _TVFn(torch.autograd.Function):
         out = torch.empty(1, dtype=torch.float32, device=xf.device)
         grad = torch.empty_like(xf) if need else None
         ws = torch.empty(lib.mmif_tv_loss_workspace() // 4 + 1, dtype=torch.float32, device=xf.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        check(lib.mmif_tv_loss(p(xf), n, h, w, weight, int(l2), p(out), p(grad), p(ws), ws.numel() * 4, T.stream_ptr()), "tv_loss")
+        check(lib.mmif_tv_loss(_p(xf), n, h, w, weight, int(l2), _p(out), _p(grad), _p(ws), ws.numel() * 4, T.stream_ptr()), "tv_loss")
         ctx.grad = grad
         return out[0]
 
@@ -184,17 +173,12 @@ class SSIM(nn.Module):
         if self._stock or small or (self._pad and not _pad_on_device(self.win_size, img1, img2)):
             return _stock.ssim_terms(img1, img2, self.win_size, self.data_range, self.use_padding, self.size_average, _stock.window(self.win_size))
         i1, i2, _ = _prep(img1, img2, img2)
-        n, _, h, w = i1.shape
-        out = torch.empty((3, n), dtype=torch.float32, device=i1.device)
-        ws = torch.empty(lib.mmif_ssim_loss_mode_workspace(n, h, w, 1) // 4 + 1, dtype=torch.float32, device=i1.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        terms = lib.mmif_ssim_terms_pad if self._pad else lib.mmif_ssim_terms
-        check(terms(p(i1), p(i2), n, h, w, self.win_size, float(self.data_range), p(out), p(ws), ws.numel() * 4, T.stream_ptr()),
-              "ssim_terms_pad" if self._pad else "ssim_terms")
+        n = i1.shape[0]
+        out = ssim_terms(i1, i2, self.win_size, self.data_range, self._pad)
         res = {'ssim': out[0], 'cs': out[1], 'sigma': out[2]}
         if self.win_size == 11 and torch.is_grad_enabled() and img2.requires_grad:
             # differentiable path: the batch-1 loss kernel per sample (loss = 1 - S with both sources = img1)
-            one = (lambda i: _PadLossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], 0, 1.0, float(self.data_range))) if self._pad else \
+            one = (lambda i: _SsimLossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], _PADDED, 0, 1.0, float(self.data_range))) if self._pad else \
                 (lambda i: _LossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], 0, 1.0, float(self.data_range), 0))
             res['ssim'] = torch.stack([1.0 - one(i) for i in range(n)])
         return res
@@ -213,8 +197,8 @@ class MS_SSIM(nn.Module):
     def forward(self, img1, img2):
         if self._stock or (self._pad and not _pad_on_device(_pad_limit('ms-ssim'), img1, img2)):
             return _stock.msssim(img1, img2, self.win_size, self.data_range, self.use_padding, self.size_average)
-        fn, mode = (_PadLossFn, _PAD_MODES['ms-ssim']) if self._pad else (_ModeLossFn, _SSIM_MODES['ms-ssim'])
-        vals = [1.0 - fn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], mode, 1.0, float(self.data_range))
+        entry, mode = (_PADDED, _PAD_MODES['ms-ssim']) if self._pad else (_UNPADDED, _SSIM_MODES['ms-ssim'])
+        vals = [1.0 - _SsimLossFn.apply(img2[i:i + 1], img1[i:i + 1], img1[i:i + 1], entry, mode, 1.0, float(self.data_range))
                 for i in range(img1.shape[0])]
         return torch.stack(vals)
 
@@ -232,9 +216,8 @@ class MSW_SSIM(nn.Module):
     def forward(self, img1, img2, imgf):
         if self._stock or (self._pad and not _pad_on_device(_pad_limit('msw-ssim'), img1, img2, imgf)):
             return _stock.mswssim(img1, img2, imgf, self.win_sizes, self.data_range, self.use_padding, self.size_average)
-        if self._pad:
-            return 1.0 - _PadLossFn.apply(imgf, img1, img2, _PAD_MODES['msw-ssim'], 1.0, float(self.data_range))
-        return 1.0 - _ModeLossFn.apply(imgf, img1, img2, _SSIM_MODES['msw-ssim'], 1.0, float(self.data_range))
+        entry, mode = (_PADDED, _PAD_MODES['msw-ssim']) if self._pad else (_UNPADDED, _SSIM_MODES['msw-ssim'])
+        return 1.0 - _SsimLossFn.apply(imgf, img1, img2, entry, mode, 1.0, float(self.data_range))
 
 
 class SSIMLoss(nn.Module):
@@ -247,12 +230,12 @@ class SSIMLoss(nn.Module):
             # reflect-padded windows (core/loss.py:42-49): the padded kernels of csrc/loss_modes.hip; CPU tensors, other dtypes and images
             # below their limits run as stock torch ops with the reference's results (core/_stock.py)
             if _pad_on_device(_pad_limit(self.mode), img1, img2, imgf):
-                return _PadLossFn.apply(imgf, img1, img2, _PAD_MODES[self.mode], float(self.weight), float(self.data_range))
+                return _SsimLossFn.apply(imgf, img1, img2, _PADDED, _PAD_MODES[self.mode], float(self.weight), float(self.data_range))
             return _stock.ssim_loss(self.mode, img1, img2, imgf, self.data_range, True, self.weight)
         if self.mode == 'ssim':
             return _LossFn.apply(imgf, img1, img2, 0, float(self.weight), float(self.data_range), 0)
         if self.mode in _SSIM_MODES:
-            return _ModeLossFn.apply(imgf, img1, img2, _SSIM_MODES[self.mode], float(self.weight), float(self.data_range))
+            return _SsimLossFn.apply(imgf, img1, img2, _UNPADDED, _SSIM_MODES[self.mode], float(self.weight), float(self.data_range))
         raise ValueError("only supported ['ssim', 'w-ssim', 'ms-ssim', 'msw-ssim'] mode")
 
 

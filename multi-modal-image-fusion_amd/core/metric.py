@@ -25,6 +25,8 @@ import torch
 from mmif import tensor as T
 from mmif._lib import check, lib
 
+from .loss import ssim_terms
+
 __all__ = [
     'calc_mean', 'calc_std', 'calc_ag', 'calc_sf', 'calc_mse', 'calc_psnr',
     'calc_cc', 'calc_scd', 'calc_entropy', 'calc_cross_ent', 'calc_mul_info',
@@ -62,11 +64,7 @@ def calc_ssim(img1, img2, win_size=11, data_range=255.0, use_padding=False, size
     # one evaluation of SSIM(a, b): the per-sample means of mmif_ssim_terms (csrc/loss_modes.hip, the kernel behind core.loss.SSIM);
     # equal-sized samples => mean of the per-sample means = the reference's mean over the whole batch.  (Rounds 1-4 went through the
     # two-source loss kernel with both sources = a, i.e. computed the same map twice.)
-    out = torch.empty((3, n), dtype=torch.float32, device=a.device)
-    ws = torch.empty(lib.mmif_ssim_loss_mode_workspace(n, h, w, 1) // 4 + 1, dtype=torch.float32, device=a.device)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    check(lib.mmif_ssim_terms(p(a), p(b), n, h, w, 11, float(data_range), p(out), p(ws), ws.numel() * 4, T.stream_ptr()), "calc_ssim")
-    return out[0].mean()
+    return ssim_terms(a, b, 11, data_range, False)[0].mean()
 
 
 # ------------------------------------------------------------------ input handling and the per-sample kernels

@@ -2,15 +2,13 @@
 // Sobel-gradient L1/L2 -- each computes the loss value AND its gradient w.r.t. the fused image
 // in the same call (reference: core/loss.py:52-110,240-344,361-385; maths in DESIGN.md / SURVEY A.4-A.5).
 // All reductions: per-block partial (wave shuffles + LDS) -> fixed-order second stage; no float atomics.
+// The SSIM window taps, map extent and constants are those of csrc/ssim_common.hpp, shared with loss_modes.hip and metric_ssim.hip.
 #include <math.h>
 
 #include "common.hpp"
+#include "ssim_common.hpp"
 
 namespace mmif {
-
-struct Win11 {
-    float t[11];
-};
 
 constexpr int LT = 16;            // tile edge
 constexpr int WIN = 11;
@@ -39,13 +37,13 @@ __device__ inline void ld16(const float* p, float (&v)[16]) {
 }
 
 __global__ __launch_bounds__(256, 2) void ssim_stats_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
-                                                            const float* __restrict__ f, int H, int W, Win11 win, float C1,
+                                                            const float* __restrict__ f, int H, int W, SsimTaps win, float C1,
                                                             float C2, float* __restrict__ maps /* [4][n][Hm][Wm] or null */,
                                                             float* __restrict__ partial, int tiles_x) {
     __shared__ __attribute__((aligned(16))) float in[3][SIN][SPI];
     __shared__ __attribute__((aligned(16))) float hb[8][SIN][SPH];
     __shared__ float red[16];
-    const int Hm = H - WIN + 1, Wm = W - WIN + 1;
+    const int Hm = H - WIN + 1, Wm = W - WIN + 1;   // ssim_map_extent(., WIN, 0), spelled out: these two kernels' code is pinned
     const int tid = threadIdx.x;
     const int mx0 = (blockIdx.x % tiles_x) * ST, my0 = (blockIdx.x / tiles_x) * ST;
     const int in_ = blockIdx.y;
@@ -133,6 +131,8 @@ __global__ __launch_bounds__(256, 2) void ssim_stats_kernel(const float* __restr
             const float ex2 = s2 == 0 ? m[3][j] : m[4][j];
             const float exf = s2 == 0 ? m[6][j] : m[7][j];
             const float sx = fmaxf(ex2 - mux * mux, 0.f);
+            // the ssim arm of ssim_pair_terms() (ssim_common.hpp), kept as this kernel's own text: it is on the train step, its code is
+            // pinned instruction for instruction, and the call in its place schedules these lines differently.  Change both together.
             const float sxf = exf - mux * muf;
             const float m1 = 2.f * mux * muf + C1, m2 = mux * mux + muf * muf + C1;
             const float v1 = 2.f * sxf + C2, v2 = sx + sf + C2;
@@ -162,12 +162,12 @@ __global__ __launch_bounds__(256, 2) void ssim_stats_kernel(const float* __restr
 // grad[y][x] = scale * ( (G^T*mA) + 2 f (G^T*mB) + x1 (G^T*mC1) + x2 (G^T*mC2) ),
 // (G^T*M)[y][x] = sum_{u,v} G[u][v] M[y-u][x-v], M zero outside the map.  Same 32 x 32 / sliding-window structure as pass 1.
 __global__ __launch_bounds__(256, 2) void ssim_grad_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
-                                                           const float* __restrict__ f, int H, int W, Win11 win,
+                                                           const float* __restrict__ f, int H, int W, SsimTaps win,
                                                            const float* __restrict__ maps, float scale,
                                                            float* __restrict__ grad, int tiles_x) {
     __shared__ __attribute__((aligned(16))) float in[4][SIN][SPI];
     __shared__ __attribute__((aligned(16))) float hb[4][SIN][SPH];
-    const int Hm = H - WIN + 1, Wm = W - WIN + 1;
+    const int Hm = H - WIN + 1, Wm = W - WIN + 1;   // ssim_map_extent(., WIN, 0), spelled out: these two kernels' code is pinned
     const int tid = threadIdx.x;
     const int x0 = (blockIdx.x % tiles_x) * ST, y0 = (blockIdx.x / tiles_x) * ST;
     const int in_ = blockIdx.y;
@@ -456,18 +456,8 @@ __global__ __launch_bounds__(256) void grad_loss_kernel(const float* __restrict_
     }
 }
 
-void gaussian_window(Win11& w) {
-    // core/loss.py:24-30: taps in double -> float32, divided by their float32 sum (== correctly
-    // rounded sum for these 11 values; pinned bit-for-bit by tests/golden/f1)
-    float g[WIN];
-    double sum = 0.0;
-    for (int i = 0; i < WIN; ++i) {
-        g[i] = (float)exp(-(double)((i - WIN / 2) * (i - WIN / 2)) / (2.0 * 1.5 * 1.5));
-        sum += (double)g[i];
-    }
-    const float fs = (float)sum;
-    for (int i = 0; i < WIN; ++i) w.t[i] = g[i] / fs;
-}
+// core/loss.py:24-30: the 11 taps at sigma 1.5 (pinned bit-for-bit by tests/golden/f1)
+static SsimTaps window11() { return ssim_taps(WIN, ssim_loss_sigma(WIN)); }
 
 }  // namespace mmif
 
@@ -488,15 +478,14 @@ extern "C" int mmif_ssim_loss(const float* img1, const float* img2, const float*
         return MMIF_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    Win11 win;
-    gaussian_window(win);
-    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
-    const int Hm = h - WIN + 1, Wm = w - WIN + 1;
+    const SsimTaps win = window11();
+    const SsimConsts<float> c = ssim_consts(data_range);
+    const int Hm = ssim_map_extent(h, WIN, 0), Wm = ssim_map_extent(w, WIN, 0);
     const int tmx = cdiv(Wm, ST), tmy = cdiv(Hm, ST);
     float* partial = (float*)workspace;
     const int np = tmx * tmy * n;
     float* maps = grad_out ? partial + (((size_t)np + 63) / 64) * 64 : nullptr;
-    hipLaunchKernelGGL(ssim_stats_kernel, dim3(tmx * tmy, n), dim3(256), 0, st, img1, img2, imgf, h, w, win, C1, C2, maps,
+    hipLaunchKernelGGL(ssim_stats_kernel, dim3(tmx * tmy, n), dim3(256), 0, st, img1, img2, imgf, h, w, win, c.C1, c.C2, maps,
                        partial, tmx);
     if (int rc = check_launch("ssim_stats")) return rc;
     hipLaunchKernelGGL(ssim_finish_kernel, dim3(1), dim3(256), 0, st, partial, np, weight, 1.f / ((float)n * Hm * Wm),
@@ -554,7 +543,7 @@ extern "C" int mmif_grad_loss(const float* img1, const float* img2, const float*
 // gradient contributions added by autograd): the same kernels as the three calls above, the pixel and Sobel kernels adding onto the
 // SSIM term's gradient, one finish kernel.  loss_out = {total, ssim, pixel, grad, total} (5 floats on the device).
 static size_t fusion_parts(int32_t n, int32_t h, int32_t w, size_t* o_px, size_t* o_gr, size_t* o_maps) {
-    const int Hm = h - WIN + 1, Wm = w - WIN + 1;
+    const int Hm = ssim_map_extent(h, WIN, 0), Wm = ssim_map_extent(w, WIN, 0);
     const size_t ns = (size_t)cdiv(Wm, ST) * cdiv(Hm, ST) * n, ngr = (size_t)cdiv(w, LT) * cdiv(h, LT) * n;
     auto up = [](size_t v) { return (v + 63) / 64 * 64; };
     *o_px = up(ns);
@@ -576,15 +565,14 @@ extern "C" int mmif_fusion_loss(const float* img1, const float* img2, const floa
         return MMIF_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    Win11 win;
-    gaussian_window(win);
-    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
-    const int Hm = h - WIN + 1, Wm = w - WIN + 1;
+    const SsimTaps win = window11();
+    const SsimConsts<float> c = ssim_consts(data_range);
+    const int Hm = ssim_map_extent(h, WIN, 0), Wm = ssim_map_extent(w, WIN, 0);
     const int tmx = cdiv(Wm, ST), tmy = cdiv(Hm, ST);
     float* ps = (float*)workspace;
     float *pp = ps + o_px, *pg = ps + o_gr, *maps = grad_out ? ps + o_maps : nullptr;
     const int ns = tmx * tmy * n;
-    hipLaunchKernelGGL(ssim_stats_kernel, dim3(tmx * tmy, n), dim3(256), 0, st, img1, img2, imgf, h, w, win, C1, C2, maps, ps, tmx);
+    hipLaunchKernelGGL(ssim_stats_kernel, dim3(tmx * tmy, n), dim3(256), 0, st, img1, img2, imgf, h, w, win, c.C1, c.C2, maps, ps, tmx);
     if (int rc = check_launch("fusion_loss ssim_stats")) return rc;
     if (grad_out) {
         const int tx = cdiv(w, ST), ty = cdiv(h, ST);

@@ -9,33 +9,17 @@
 // (constant x per-sample x per-pixel gamma), the quantity is ssim or cs.  gamma depends only on the source images, so the
 // gradient w.r.t. the fused image flows through the ssim / cs maps alone, exactly as in the reference's autograd graph.
 // Not on the train.py hot path ('ssim' keeps its own tuned kernels); value + d/dimgf in one call like the other losses.
+// Taps, pair terms, map extent, C1 / C2 and the pyramid step are those of csrc/ssim_common.hpp, shared with loss.hip and metric_ssim.hip.
 #include <math.h>
 
 #include "common.hpp"
-#include "ssim_pool.hpp"
+#include <type_traits>
+
+#include "ssim_common.hpp"
 
 namespace mmif {
 
-struct WinK {
-    float t[11];
-};
-
 constexpr int MT_ = 16;   // tile edge
-
-static void make_window(WinK& w, int k) {
-    // core/loss.py:24-39: taps in double -> float32, divided by their float32 sum.  The sum is torch's float32 sum of a short vector:
-    // four interleaved partial sums combined pairwise.  For 5, 7, 9 and 11 taps that is the correctly rounded sum; for 3 taps it is one
-    // ulp above it (golden F20 'msw-ssim_255' shows the difference, tests/test_loss_oracle_cpu.py pins the taps).
-    const double sigma = k == 11 ? 1.5 : 0.15 * (k - 1);
-    float g[11];
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i < k; ++i) {
-        g[i] = (float)exp(-(double)((i - k / 2) * (i - k / 2)) / (2.0 * sigma * sigma));
-        acc[i & 3] += g[i];
-    }
-    const float fs = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-    for (int i = 0; i < 11; ++i) w.t[i] = i < k ? g[i] / fs : 0.f;
-}
 
 // ------------------------------------------------------------------ pass 1: values + weighted adjoint inputs
 // per map pixel and pair p (x1|x2 vs f): Q_p = ssim or cs; effective weight g_p = c_p * (w_p ? w_p[sample] : 1) * (pixel gamma?)
@@ -45,7 +29,7 @@ static void make_window(WinK& w, int k) {
 // the tile loader reads image pixel (reflect(y - P), reflect(x - P)); nothing after the loader changes.
 template <int WIN, int PAD>
 __global__ __launch_bounds__(256) void ssimx_stats_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
-                                                          const float* __restrict__ f, int H, int W, WinK win, float C1, float C2,
+                                                          const float* __restrict__ f, int H, int W, SsimTaps win, float C1, float C2,
                                                           float ca, float cb, const float* __restrict__ wa, const float* __restrict__ wb,
                                                           int pix_gamma, int quantity_cs, float* __restrict__ maps,
                                                           float* __restrict__ partial, int tiles_x) {
@@ -53,7 +37,7 @@ __global__ __launch_bounds__(256) void ssimx_stats_kernel(const float* __restric
     __shared__ float in[3][LIN][LIN + 1];
     __shared__ float hb[8][LIN][MT_ + 1];
     __shared__ float red[16];
-    const int Hm = PAD ? H : H - WIN + 1, Wm = PAD ? W : W - WIN + 1;
+    const int Hm = ssim_map_extent(H, WIN, PAD), Wm = ssim_map_extent(W, WIN, PAD);
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int mx0 = (blockIdx.x % tiles_x) * MT_, my0 = (blockIdx.x / tiles_x) * MT_;
     const int in_ = blockIdx.y;
@@ -65,10 +49,8 @@ __global__ __launch_bounds__(256) void ssimx_stats_kernel(const float* __restric
         if (PAD) {   // padded row my0 + py mirrors image row reflect(my0 + py - P); P < H, W, so one reflection lands inside
             constexpr int P = WIN / 2;
             ok = (y < H + 2 * P) && (x < W + 2 * P);
-            y -= P;
-            x -= P;
-            y = y < 0 ? -y : (y >= H ? 2 * (H - 1) - y : y);
-            x = x < 0 ? -x : (x >= W ? 2 * (W - 1) - x : x);
+            y = reflect_idx(y - P, H);
+            x = reflect_idx(x - P, W);
             if (!ok) y = x = 0;
         }
         const long long i = ibase + (long long)y * W + x;
@@ -127,25 +109,11 @@ __global__ __launch_bounds__(256) void ssimx_stats_kernel(const float* __restric
             const float exf = s == 0 ? m[6] : m[7];
             const float gw = s == 0 ? g1 : g2;
             const float sxf = exf - mux * muf;
-            const float m1 = 2.f * mux * muf + C1, m2 = mux * mux + muf * muf + C1;
-            const float v1 = 2.f * sxf + C2, v2 = sx + sf + C2;
-            float Q, Ap, Bp, Cp;
-            if (quantity_cs) {
-                Q = v1 / v2;
-                Bp = -(Q / v2) * kf;
-                Cp = 2.f / v2;
-                Ap = -mux * Cp - 2.f * muf * Bp;
-            } else {
-                const float inv = 1.f / (m2 * v2);
-                Q = m1 * v1 * inv;
-                Bp = -(Q / v2) * kf;
-                Cp = 2.f * m1 * inv;
-                Ap = 2.f * mux * v1 * inv - 2.f * muf * Q / m2 - 2.f * mux * m1 * inv - 2.f * muf * Bp;
-            }
-            sums[s] = gw * Q;
-            A += gw * Ap;
-            B += gw * Bp;
-            Cs[s] = gw * Cp;
+            const SsimPair t = ssim_pair_terms(quantity_cs != 0, mux, muf, sx, sf, sxf, kf, C1, C2);
+            sums[s] = gw * t.Q;
+            A += gw * t.A;
+            B += gw * t.B;
+            Cs[s] = gw * t.C;
         }
         sums[2] = sg1;
         sums[3] = sg2;
@@ -187,7 +155,7 @@ __device__ __forceinline__ float fold_tap(const float* __restrict__ wl, int c, i
 
 template <int WIN, int PAD>
 __global__ __launch_bounds__(256) void ssimx_grad_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
-                                                         const float* __restrict__ f, int H, int W, WinK win,
+                                                         const float* __restrict__ f, int H, int W, SsimTaps win,
                                                          const float* __restrict__ maps, float scale, int accumulate,
                                                          float* __restrict__ grad, int tiles_x) {
     constexpr int LIN = MT_ + WIN - 1;
@@ -195,7 +163,7 @@ __global__ __launch_bounds__(256) void ssimx_grad_kernel(const float* __restrict
     __shared__ float in[4][LIN][LIN + 1];
     __shared__ float hb[4][LIN][MT_ + 1];
     __shared__ float wl[WIN];
-    const int Hm = PAD ? H : H - WIN + 1, Wm = PAD ? W : W - WIN + 1;
+    const int Hm = ssim_map_extent(H, WIN, PAD), Wm = ssim_map_extent(W, WIN, PAD);
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int x0 = (blockIdx.x % tiles_x) * MT_, y0 = (blockIdx.x / tiles_x) * MT_;
     const int in_ = blockIdx.y;
@@ -294,8 +262,8 @@ __global__ void value_finish_kernel(const float* __restrict__ sums, int n, float
 }
 
 // ------------------------------------------------------------------ ms-ssim pyramid
-// forward step: avg_pool_pad_kernel<float> of ssim_pool.hpp (shared with the metric side); its adjoint, accumulated into the finer
-// level's gradient
+// forward step: avg_pool_pad3 of ssim_common.hpp (shared with the metric side); its adjoint, accumulated into the finer level's
+// gradient
 __global__ void avg_pool_pad_bwd_kernel(const float* __restrict__ gc, float* __restrict__ gf, int n, int h, int w) {
     const int ho = (h + 1) / 2, wo = (w + 1) / 2;
     const long long total = (long long)n * h * w;
@@ -390,10 +358,8 @@ struct SsimArgs {
 template <int WIN, int PAD = 0>
 static int run_stats(const SsimArgs& a, float ca, float cb, const float* wa, const float* wb, int pix, int cs, float* maps,
                      float* partial, float* sums) {
-    WinK win;
-    make_window(win, WIN);
-    const int Hm = PAD ? a.h : a.h - WIN + 1, Wm = PAD ? a.w : a.w - WIN + 1;
-    const int tmx = cdiv(Wm, MT_), tmy = cdiv(Hm, MT_);
+    const SsimTaps win = ssim_taps(WIN, ssim_loss_sigma(WIN));
+    const int tmx = cdiv(ssim_map_extent(a.w, WIN, PAD), MT_), tmy = cdiv(ssim_map_extent(a.h, WIN, PAD), MT_);
     hipLaunchKernelGGL((ssimx_stats_kernel<WIN, PAD>), dim3(tmx * tmy, a.n), dim3(256), 0, a.st, a.x1, a.x2, a.f, a.h, a.w, win, a.C1, a.C2, ca,
                        cb, wa, wb, pix, cs, maps, partial, tmx);
     if (int rc = check_launch("ssimx_stats")) return rc;
@@ -402,16 +368,22 @@ static int run_stats(const SsimArgs& a, float ca, float cb, const float* wa, con
 }
 template <int WIN, int PAD = 0>
 static int run_grad(const SsimArgs& a, const float* maps, float scale, int accumulate, float* grad) {
-    WinK win;
-    make_window(win, WIN);
+    const SsimTaps win = ssim_taps(WIN, ssim_loss_sigma(WIN));
     const int tx = cdiv(a.w, MT_), ty = cdiv(a.h, MT_);
     hipLaunchKernelGGL((ssimx_grad_kernel<WIN, PAD>), dim3(tx * ty, a.n), dim3(256), 0, a.st, a.x1, a.x2, a.f, a.h, a.w, win, maps, scale,
                        accumulate, grad, tx);
     return check_launch("ssimx_grad");
 }
-static int ew_grid(long long total) {
-    long long b = (total + 255) / 256;
-    return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+// f(std::integral_constant<int, K>) for the window size k of the loss side, 3 / 5 / 7 / 9 / 11 (the entry points have checked it)
+template <typename F>
+static int for_window(int k, F&& f) {
+    switch (k) {
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+        default: return f(std::integral_constant<int, 11>{});
+    }
 }
 
 }  // namespace mmif
@@ -423,12 +395,8 @@ extern "C" size_t mmif_ssim_loss_mode_workspace(int32_t n, int32_t h, int32_t w,
     const size_t tiles = (size_t)cdiv(h, MT_) * cdiv(w, MT_);
     size_t fl = 4 * n * tiles + 26 * (size_t)n + 64 + 4 * (size_t)n * h * w;
     if (mode == 2) {   // ms-ssim: 3 pyramid images + 1 gradient per coarser level
-        size_t hl = h, wl = w;
-        for (int l = 1; l < 5; ++l) {
-            hl = (hl + 1) / 2;
-            wl = (wl + 1) / 2;
-            fl += 4 * (size_t)n * hl * wl + 64;
-        }
+        const SsimPyramid py = ssim_pyramid(h, w);
+        for (int l = 1; l < SSIM_LEVELS; ++l) fl += 4 * (size_t)n * py.pixels(l) + 64;
     }
     return fl * sizeof(float);
 }
@@ -439,7 +407,7 @@ template <int PAD>
 static int ssim_modes_run(const float* img1, const float* img2, const float* imgf, int32_t n, int32_t h, int32_t w, float weight,
                           float data_range, int32_t mode, float* loss_out, float* grad_out, void* workspace, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
+    const SsimConsts<float> c = ssim_consts(data_range);
     const size_t tiles = (size_t)cdiv(h, MT_) * cdiv(w, MT_);
     float* partial = (float*)workspace;
     float* sums = partial + 4 * n * tiles;
@@ -448,9 +416,9 @@ static int ssim_modes_run(const float* img1, const float* img2, const float* img
     float* vals = wb + n;
     float* wts = vals + 10 * n;
     float* maps = wts + 10 * n;
-    SsimArgs a{img1, img2, imgf, n, h, w, C1, C2, st};
+    SsimArgs a{img1, img2, imgf, n, h, w, c.C1, c.C2, st};
     if (mode == 0) {   // ssim (PAD only): weight * (1 - (mean S1 + mean S2) / 2)
-        const float cnt = (float)h * (float)w;
+        const float cnt = ssim_map_count(h, w, 11, PAD);
         if (int rc = run_stats<11, PAD>(a, 1.f, 1.f, nullptr, nullptr, 0, 0, grad_out ? maps : nullptr, partial, sums)) return rc;
         hipLaunchKernelGGL(value_finish_kernel, dim3(1), dim3(64), 0, st, sums, n, 1.f / ((float)n * cnt), weight, 0.5f, 1, loss_out);
         if (int rc = check_launch("ssim_pad_finish")) return rc;
@@ -458,7 +426,7 @@ static int ssim_modes_run(const float* img1, const float* img2, const float* img
         return MMIF_OK;
     }
     if (mode == 1) {   // w-ssim
-        const float cnt = PAD ? (float)h * (float)w : (float)(h - 10) * (float)(w - 10);
+        const float cnt = ssim_map_count(h, w, 11, PAD);
         if (int rc = run_stats<11, PAD>(a, 1.f, 1.f, nullptr, nullptr, 0, 0, nullptr, partial, sums)) return rc;   // sigma means
         hipLaunchKernelGGL(wssim_gamma_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, sums, n, 1.f / cnt, wa, wb);
         if (int rc = check_launch("wssim_gamma")) return rc;
@@ -470,57 +438,41 @@ static int ssim_modes_run(const float* img1, const float* img2, const float* img
     }
     if (mode == 3) {   // msw-ssim
         int first = 1;
-#define MSW_STEP(K)                                                                                                                   \
-    {                                                                                                                                 \
-        const float cnt = PAD ? (float)h * (float)w : (float)(h - K + 1) * (float)(w - K + 1);                                        \
-        if (int rc = run_stats<K, PAD>(a, 1.f, 1.f, nullptr, nullptr, 1, 0, grad_out ? maps : nullptr, partial, sums)) return rc;      \
-        hipLaunchKernelGGL(value_finish_kernel, dim3(1), dim3(64), 0, st, sums, n, 1.f / ((float)n * cnt), weight, 0.2f, first,      \
-                           loss_out);                                                                                                 \
-        if (int rc = check_launch("mswssim_finish")) return rc;                                                                       \
-        if (grad_out)                                                                                                                 \
-            if (int rc = run_grad<K, PAD>(a, maps, -weight * 0.2f / ((float)n * cnt), first ? 0 : 1, grad_out)) return rc;            \
-        first = 0;                                                                                                                    \
-    }
-        MSW_STEP(11) MSW_STEP(9) MSW_STEP(7) MSW_STEP(5) MSW_STEP(3)
-#undef MSW_STEP
+        auto step = [&](auto win) -> int {
+            constexpr int K = decltype(win)::value;
+            const float cnt = ssim_map_count(h, w, K, PAD);
+            if (int rc = run_stats<K, PAD>(a, 1.f, 1.f, nullptr, nullptr, 1, 0, grad_out ? maps : nullptr, partial, sums)) return rc;
+            hipLaunchKernelGGL(value_finish_kernel, dim3(1), dim3(64), 0, st, sums, n, 1.f / ((float)n * cnt), weight, 0.2f, first, loss_out);
+            if (int rc = check_launch("mswssim_finish")) return rc;
+            if (grad_out)
+                if (int rc = run_grad<K, PAD>(a, maps, -weight * 0.2f / ((float)n * cnt), first ? 0 : 1, grad_out)) return rc;
+            first = 0;
+            return MMIF_OK;
+        };
+        for (int k : {11, 9, 7, 5, 3})
+            if (int rc = for_window(k, step)) return rc;
         return MMIF_OK;
     }
     // ---- ms-ssim
-    int hs[5], wsz[5];
-    hs[0] = h;
-    wsz[0] = w;
-    for (int l = 1; l < 5; ++l) {
-        hs[l] = (hs[l - 1] + 1) / 2;
-        wsz[l] = (wsz[l - 1] + 1) / 2;
-    }
-    if (!PAD) MMIF_REQUIRE(hs[4] >= 11 && wsz[4] >= 11, "ssim_loss_mode: ms-ssim needs images of at least 161x161 (11x11 window on level 4); got %dx%d", h, w);
+    const SsimPyramid py = ssim_pyramid(h, w);
+    if (!PAD) MMIF_REQUIRE(py.h[4] >= 11 && py.w[4] >= 11, "ssim_loss_mode: ms-ssim needs images of at least 161x161 (11x11 window on level 4); got %dx%d", h, w);
     float* pyr = maps + 4 * (size_t)n * h * w;
-    const float* lx1[5] = {img1};
-    const float* lx2[5] = {img2};
-    const float* lf[5] = {imgf};
+    const float* lv[5][3] = {{img1, img2, imgf}};   // x1, x2, f of every level
     float* lg[5] = {grad_out};
     for (int l = 1; l < 5; ++l) {
-        const size_t sz = (size_t)n * hs[l] * wsz[l];
-        float* p1 = pyr;
-        float* p2 = p1 + sz;
-        float* pf = p2 + sz;
-        lg[l] = pf + sz;
+        const size_t sz = (size_t)n * py.pixels(l);
+        float* const dst[3] = {pyr, pyr + sz, pyr + 2 * sz};
+        lg[l] = pyr + 3 * sz;
         pyr = lg[l] + sz;
-        const int grid = ew_grid((long long)sz);
-        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lx1[l - 1], p1, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lx2[l - 1], p2, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lf[l - 1], pf, n, hs[l - 1], wsz[l - 1]);
-        if (int rc = check_launch("avg_pool_pad")) return rc;
-        lx1[l] = p1;
-        lx2[l] = p2;
-        lf[l] = pf;
+        if (int rc = avg_pool_pad3(lv[l - 1], dst, n, py.h[l - 1], py.w[l - 1], st, "avg_pool_pad")) return rc;
+        for (int q = 0; q < 3; ++q) lv[l][q] = dst[q];
     }
     MsMeta meta;
     const float msw[5] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
     for (int l = 0; l < 5; ++l) {
         meta.w[l] = msw[l];
-        meta.inv_nmap[l] = 1.f / (PAD ? (float)hs[l] * (float)wsz[l] : (float)(hs[l] - 10) * (float)(wsz[l] - 10));
-        SsimArgs al{lx1[l], lx2[l], lf[l], n, hs[l], wsz[l], C1, C2, st};
+        meta.inv_nmap[l] = 1.f / ssim_map_count(py.h[l], py.w[l], 11, PAD);
+        SsimArgs al{lv[l][0], lv[l][1], lv[l][2], n, py.h[l], py.w[l], c.C1, c.C2, st};
         if (int rc = run_stats<11, PAD>(al, 1.f, 1.f, nullptr, nullptr, 0, l < 4 ? 1 : 0, nullptr, partial, sums)) return rc;
         // vals[p][l][b] <- sums[p][b]
         (void)hipMemcpyAsync(vals + (0 * 5 + l) * n, sums, n * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -530,12 +482,12 @@ static int ssim_modes_run(const float* img1, const float* img2, const float* img
     if (int rc = check_launch("ms_weights")) return rc;
     if (!grad_out) return MMIF_OK;
     for (int l = 4; l >= 0; --l) {
-        SsimArgs al{lx1[l], lx2[l], lf[l], n, hs[l], wsz[l], C1, C2, st};
+        SsimArgs al{lv[l][0], lv[l][1], lv[l][2], n, py.h[l], py.w[l], c.C1, c.C2, st};
         if (int rc = run_stats<11, PAD>(al, 1.f, 1.f, wts + (0 * 5 + l) * n, wts + (1 * 5 + l) * n, 0, l < 4 ? 1 : 0, maps, partial, sums)) return rc;
         if (int rc = run_grad<11, PAD>(al, maps, 1.f, 0, lg[l])) return rc;
         if (l < 4) {
-            hipLaunchKernelGGL(avg_pool_pad_bwd_kernel, dim3(ew_grid((long long)n * hs[l] * wsz[l])), dim3(256), 0, st, lg[l + 1], lg[l], n,
-                               hs[l], wsz[l]);
+            hipLaunchKernelGGL(avg_pool_pad_bwd_kernel, dim3(ew_grid((long long)n * py.h[l] * py.w[l])), dim3(256), 0, st, lg[l + 1], lg[l], n,
+                               py.h[l], py.w[l]);
             if (int rc = check_launch("avg_pool_pad_bwd")) return rc;
         }
     }
@@ -600,22 +552,15 @@ static int ssim_terms_run(const char* who, const float* img1, const float* img2,
         return MMIF_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
+    const SsimConsts<float> c = ssim_consts(data_range);
     const size_t tiles = (size_t)cdiv(h, MT_) * cdiv(w, MT_);
     float* partial = (float*)workspace;
     float* sums = partial + 4 * n * tiles;
-    SsimArgs a{img1, img1, img2, n, h, w, C1, C2, st};   // pair 1 = (img1, img2); pair 2 unused
-    const float inv = 1.f / (PAD ? (float)h * (float)w : (float)(h - win_size + 1) * (float)(w - win_size + 1));
+    SsimArgs a{img1, img1, img2, n, h, w, c.C1, c.C2, st};   // pair 1 = (img1, img2); pair 2 unused
+    const float inv = 1.f / ssim_map_count(h, w, win_size, PAD);
     for (int cs = 0; cs < 2; ++cs) {
-        int rc;
-        switch (win_size) {
-            case 3: rc = run_stats<3, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            case 5: rc = run_stats<5, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            case 7: rc = run_stats<7, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            case 9: rc = run_stats<9, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-            default: rc = run_stats<11, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); break;
-        }
-        if (rc) return rc;
+        auto stats = [&](auto win) { return run_stats<decltype(win)::value, PAD>(a, 1.f, 0.f, nullptr, nullptr, 0, cs, nullptr, partial, sums); };
+        if (int rc = for_window(win_size, stats)) return rc;
         hipLaunchKernelGGL(pick_row_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, sums, n, 0, inv, out + cs * n);
         if (cs == 1) hipLaunchKernelGGL(pick_row_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, sums, n, 2, inv, out + 2 * n);
         if (int rc2 = check_launch("ssim_terms pick")) return rc2;
@@ -657,12 +602,8 @@ extern "C" int mmif_tv_loss(const float* x, int32_t n, int32_t h, int32_t w, flo
 extern "C" size_t mmif_metric_msssim_workspace(int32_t n, int32_t h, int32_t w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
     size_t fl = 4 * (size_t)n * cdiv(h, MT_) * cdiv(w, MT_) + 4 * (size_t)n + 64;
-    size_t hl = h, wl = w;
-    for (int l = 1; l < 5; ++l) {
-        hl = (hl + 1) / 2;
-        wl = (wl + 1) / 2;
-        fl += 3 * (size_t)n * hl * wl + 64;
-    }
+    const SsimPyramid py = ssim_pyramid(h, w);
+    for (int l = 1; l < SSIM_LEVELS; ++l) fl += 3 * (size_t)n * py.pixels(l) + 64;
     return fl * sizeof(float);
 }
 
@@ -679,39 +620,25 @@ extern "C" int mmif_metric_msssim(const float* a, const float* b, const float* f
     }
     if (b == nullptr) b = a;
     hipStream_t st = (hipStream_t)stream;
-    const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
+    const SsimConsts<float> c = ssim_consts(data_range);
     float* partial = (float*)workspace;
     float* sums = partial + 4 * (size_t)n * cdiv(h, MT_) * cdiv(w, MT_);
     float* pyr = sums + 4 * n + 64;
-    int hs[5], wsz[5];
-    const float* la[5] = {a};
-    const float* lb[5] = {b};
-    const float* lf[5] = {f};
-    hs[0] = h;
-    wsz[0] = w;
+    const SsimPyramid py = ssim_pyramid(h, w);
+    const float* lv[5][3] = {{a, b, f}};   // a, b, f of every level
     for (int l = 1; l < 5; ++l) {
-        hs[l] = (hs[l - 1] + 1) / 2;
-        wsz[l] = (wsz[l - 1] + 1) / 2;
-        const size_t sz = (size_t)n * hs[l] * wsz[l];
-        float* pa = pyr;
-        float* pb = pa + sz;
-        float* pf = pb + sz;
-        pyr = pf + sz + 64;
-        const int grid = ew_grid((long long)sz);
-        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, la[l - 1], pa, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lb[l - 1], pb, n, hs[l - 1], wsz[l - 1]);
-        hipLaunchKernelGGL(avg_pool_pad_kernel<float>, dim3(grid), dim3(256), 0, st, lf[l - 1], pf, n, hs[l - 1], wsz[l - 1]);
-        if (int rc = check_launch("metric_msssim pool")) return rc;
-        la[l] = pa;
-        lb[l] = pb;
-        lf[l] = pf;
+        const size_t sz = (size_t)n * py.pixels(l);
+        float* const dst[3] = {pyr, pyr + sz, pyr + 2 * sz};
+        pyr += 3 * sz + 64;
+        if (int rc = avg_pool_pad3(lv[l - 1], dst, n, py.h[l - 1], py.w[l - 1], st, "metric_msssim pool")) return rc;
+        for (int q = 0; q < 3; ++q) lv[l][q] = dst[q];
     }
     for (int slot = 0; slot < 6; ++slot) {
         const int l = slot == 5 ? 0 : slot;
         const int cs = slot < 4 ? 1 : 0;
-        SsimArgs al{la[l], lb[l], lf[l], n, hs[l], wsz[l], C1, C2, st};
+        SsimArgs al{lv[l][0], lv[l][1], lv[l][2], n, py.h[l], py.w[l], c.C1, c.C2, st};
         if (int rc = run_stats<11>(al, 1.f, 1.f, nullptr, nullptr, 0, cs, nullptr, partial, sums)) return rc;
-        const float inv = 1.f / ((float)(hs[l] - 10) * (float)(wsz[l] - 10));
+        const float inv = 1.f / ssim_map_count(py.h[l], py.w[l], 11, 0);
         for (int p = 0; p < 2; ++p) hipLaunchKernelGGL(pick_row_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, sums, n, p, inv, out + (p * 6 + slot) * n);
         if (int rc = check_launch("metric_msssim pick")) return rc;
     }

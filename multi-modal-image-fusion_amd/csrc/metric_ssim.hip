@@ -18,32 +18,23 @@
 #include <math.h>
 
 #include "common.hpp"
-#include "ssim_pool.hpp"
+#include "ssim_common.hpp"
 
 namespace mmif {
 
 constexpr int MS_T = 16;      // map tile edge
-constexpr int MS_KMAX = 11;   // largest window
+constexpr int MS_KMAX = SSIM_KMAX;   // largest window
 constexpr int MS_LIN = MS_T + MS_KMAX - 1;
 
 struct MetricWin {
     float w[MS_KMAX * MS_KMAX];   // w[i * k + j] = fp32(t_i * t_j)
 };
 
-// the reference's _gaussian_kernel(k, 1.5) and create_window: taps[k], win[k][k].  torch's float32 sum of a short vector runs four
-// interleaved partial sums and combines them pairwise (see make_window in loss_modes.hip); tests/test_ssim_metric_oracle_cpu.py pins
-// every k = 1..11 bit for bit.
-static void metric_window(int k, float* taps, float* win) {
-    float g[MS_KMAX];
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i < k; ++i) {
-        g[i] = (float)exp(-(double)((i - k / 2) * (i - k / 2)) / (2.0 * 1.5 * 1.5));
-        acc[i & 3] += g[i];
-    }
-    const float fs = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-    for (int i = 0; i < k; ++i) taps[i] = g[i] / fs;
+// the reference's create_window on the taps of _gaussian_kernel(k, 1.5) (ssim_taps of ssim_common.hpp): win[k][k], the fp32 products;
+// tests/test_ssim_metric_oracle_cpu.py pins every k = 1..11 bit for bit.
+static void metric_window(const SsimTaps& taps, int k, float* win) {
     for (int i = 0; i < k; ++i)
-        for (int j = 0; j < k; ++j) win[i * k + j] = taps[i] * taps[j];
+        for (int j = 0; j < k; ++j) win[i * k + j] = taps.t[i] * taps.t[j];
 }
 
 // one 16 x 16 tile of the maps of sample blockIdx.x / tiles.  P = 0 without padding, k / 2 with.  ssim_map, cs_map [n][Hm][Wm] and
@@ -157,8 +148,8 @@ static MapGeom map_geom(int h, int w, int win_size, int use_padding) {
     g.k = win_size < h ? win_size : h;
     g.k = g.k < w ? g.k : w;
     g.p = use_padding ? g.k / 2 : 0;
-    g.hm = h + 2 * g.p - g.k + 1;
-    g.wm = w + 2 * g.p - g.k + 1;
+    g.hm = ssim_map_extent(h, g.k, use_padding);
+    g.wm = ssim_map_extent(w, g.k, use_padding);
     g.tiles_x = cdiv(g.wm, MS_T);
     g.tiles = g.tiles_x * cdiv(g.hm, MS_T);
     return g;
@@ -169,11 +160,10 @@ template <typename TIN>
 static int run_maps(const TIN* x1, const TIN* x2, int n, int h, int w, const MapGeom& g, double data_range, float* ssim_map, float* cs_map,
                     double* partial, hipStream_t st) {
     MetricWin win;
-    float taps[MS_KMAX];
     memset(&win, 0, sizeof(win));
-    metric_window(g.k, taps, win.w);
-    const double C1 = (0.01 * data_range) * (0.01 * data_range), C2 = (0.03 * data_range) * (0.03 * data_range);
-    hipLaunchKernelGGL((metric_ssim_kernel<TIN>), dim3((unsigned)n * g.tiles), dim3(256), 0, st, x1, x2, h, w, g.hm, g.wm, g.k, g.p, win, C1, C2,
+    metric_window(ssim_taps(g.k, 1.5), g.k, win.w);
+    const SsimConsts<double> c = ssim_consts(data_range);
+    hipLaunchKernelGGL((metric_ssim_kernel<TIN>), dim3((unsigned)n * g.tiles), dim3(256), 0, st, x1, x2, h, w, g.hm, g.wm, g.k, g.p, win, c.C1, c.C2,
                        ssim_map, cs_map, partial, g.tiles_x, g.tiles);
     return check_launch("metric_ssim");
 }
@@ -189,7 +179,9 @@ using namespace mmif;
 extern "C" int mmif_metric_ssim_window(int32_t win_size, float* taps, float* window) {
     MMIF_REQUIRE(win_size >= 1 && win_size <= MS_KMAX, "metric_ssim_window: win_size must be 1..11 (got %d)", win_size);
     MMIF_REQUIRE(taps && window, "metric_ssim_window: NULL argument");
-    metric_window(win_size, taps, window);
+    const SsimTaps t = ssim_taps(win_size, 1.5);
+    for (int i = 0; i < win_size; ++i) taps[i] = t.t[i];
+    metric_window(t, win_size, window);
     return MMIF_OK;
 }
 
@@ -228,18 +220,9 @@ extern "C" int mmif_metric_ssim_maps(const float* img1, const float* img2, int32
 extern "C" size_t mmif_metric_msssim_any_workspace(int32_t n, int32_t h, int32_t w) {
     if (n < 1 || h < 9 || w < 9) return 0;
     size_t bytes = align256(2 * (size_t)n * cdiv(h + 1, MS_T) * cdiv(w + 1, MS_T) * sizeof(double));   // (h + 1) x (w + 1): padded even window
-    size_t hl = h, wl = w;
-    for (int l = 1; l < 5; ++l) {
-        hl = (hl + 1) / 2;
-        wl = (wl + 1) / 2;
-        bytes += 3 * align256((size_t)n * hl * wl * sizeof(double));
-    }
+    const SsimPyramid py = ssim_pyramid(h, w);
+    for (int l = 1; l < SSIM_LEVELS; ++l) bytes += 3 * align256((size_t)n * py.pixels(l) * sizeof(double));
     return bytes;
-}
-
-static int ew_grid(long long total) {
-    long long b = (total + 255) / 256;
-    return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
 
 // one level of one pair: the window pass, then the per-sample means into out rows
@@ -280,28 +263,21 @@ extern "C" int mmif_metric_msssim_any(const float* a, const float* b, const floa
                                          out + (p * 6 + 0) * (long long)n, dup, st))
             return rc;
     // levels 1..4 on fp64 pyramids (the pooling of fp32 pixels is exact enough in double to be the definition's)
-    double* lv[3] = {nullptr, nullptr, nullptr};   // a, b, f of the previous level
-    int hl = h, wl = w;
+    const SsimPyramid py = ssim_pyramid(h, w);
+    const float* const lv0[3] = {a, b, f};
+    double* lv[3] = {nullptr, nullptr, nullptr};   // a, b (unused where b == NULL), f of the previous level
     for (int l = 1; l < 5; ++l) {
-        const int ho = (hl + 1) / 2, wo = (wl + 1) / 2;
-        const size_t sz = (size_t)n * ho * wo;
-        const int grid = ew_grid((long long)sz);
         double* cur[3];
         for (int q = 0; q < 3; ++q) {
             cur[q] = (double*)wsp;
-            wsp += align256(sz * sizeof(double));
-            if (q == 1 && b == nullptr) continue;
-            if (l == 1) {
-                const float* s0 = q == 0 ? a : (q == 1 ? b : f);
-                hipLaunchKernelGGL((avg_pool_pad_kernel<double, float>), dim3(grid), dim3(256), 0, st, s0, cur[q], n, hl, wl);
-            } else {
-                hipLaunchKernelGGL(avg_pool_pad_kernel<double>, dim3(grid), dim3(256), 0, st, (const double*)lv[q], cur[q], n, hl, wl);
-            }
+            wsp += align256((size_t)n * py.pixels(l) * sizeof(double));
         }
-        if (int rc = check_launch("metric_msssim_any pool")) return rc;
+        const double* const prev[3] = {lv[0], b != nullptr ? lv[1] : nullptr, lv[2]};
+        if (int rc = l == 1 ? avg_pool_pad3(lv0, cur, n, h, w, st, "metric_msssim_any pool")
+                            : avg_pool_pad3(prev, cur, n, py.h[l - 1], py.w[l - 1], st, "metric_msssim_any pool"))
+            return rc;
         for (int q = 0; q < 3; ++q) lv[q] = cur[q];
-        hl = ho;
-        wl = wo;
+        const int hl = py.h[l], wl = py.w[l];
         for (int p = 0; p < npairs; ++p) {
             double* row = out + (p * 6 + l) * (long long)n;
             if (int rc = msssim_level<double>(lv[p], lv[2], n, hl, wl, win_size, use_padding, data_range, partial, l == 4 ? row : nullptr,

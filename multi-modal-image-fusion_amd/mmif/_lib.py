@@ -209,6 +209,12 @@ SIGNATURES = {
     "mmif_ssim_loss_pad_workspace": (_sz, [_i32, _i32, _i32, _i32]),
     "mmif_ssim_loss_pad": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_ssim_terms_pad": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
+    "mmif_tv_loss_workspace": (_sz, []),
+    "mmif_tv_loss": (_i32, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "mmif_pixel_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "mmif_grad_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "mmif_fusion_loss_workspace": (_sz, [_i32, _i32, _i32]),
+    "mmif_fusion_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_metric_moments_workspace": (_sz, [_i32] * 4),
     "mmif_metric_moments": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "mmif_metric_hist": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -224,12 +230,6 @@ SIGNATURES = {
     "mmif_metric_msssim_any_workspace": (_sz, [_i32] * 3),
     "mmif_metric_msssim_any": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _sz, _vp]),
     "mmif_metric_ssim_window": (_i32, [_i32, _vp, _vp]),
-    "mmif_tv_loss_workspace": (_sz, []),
-    "mmif_tv_loss": (_i32, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "mmif_pixel_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "mmif_grad_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "mmif_fusion_loss_workspace": (_sz, [_i32, _i32, _i32]),
-    "mmif_fusion_loss": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mmif_patch_feed": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mmif_clip_adam_workspace": (_sz, [_i64]),
     "mmif_clip_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _vp, _vp, _sz, _vp]),

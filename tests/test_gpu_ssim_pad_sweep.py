@@ -231,7 +231,7 @@ def test_ms_ssim_and_msw_ssim_modules_padded(no_stock):
 
 
 def test_unpadded_options_keep_their_bits():
-    """use_padding=False is the entry point it was: the same bits as _LossFn / _ModeLossFn called directly"""
+    """use_padding=False is the entry point it was: the same bits as _LossFn / _SsimLossFn(_UNPADDED) called directly"""
     from core import loss as L
     a, b, f = dev(*LC.triple('rand', 40, 56, 2))
     big = dev(*LC.triple('cf', 161, 163, 1))
@@ -240,10 +240,10 @@ def test_unpadded_options_keep_their_bits():
         if mode == 'ssim':
             l0, g0 = run(lambda x, y, z: L._LossFn.apply(z, x, y, 0, 0.7, 1.0, 0), *xs)
         else:
-            l0, g0 = run(lambda x, y, z: L._ModeLossFn.apply(z, x, y, L._SSIM_MODES[mode], 0.7, 1.0), *xs)
+            l0, g0 = run(lambda x, y, z: L._SsimLossFn.apply(z, x, y, L._UNPADDED, L._SSIM_MODES[mode], 0.7, 1.0), *xs)
         assert torch.equal(l, l0) and torch.equal(g, g0), mode
     v, g = run(L.MSW_SSIM(), a, b, f)
-    v0, g0 = run(lambda x, y, z: 1.0 - L._ModeLossFn.apply(z, x, y, 3, 1.0, 1.0), a, b, f)
+    v0, g0 = run(lambda x, y, z: 1.0 - L._SsimLossFn.apply(z, x, y, L._UNPADDED, 3, 1.0, 1.0), a, b, f)
     assert torch.equal(v, v0) and torch.equal(g, g0)
 
 
