@@ -789,12 +789,18 @@ int32_t mmif_reduce_defer_pending(void);
  * Returns 1 and fills *out, or 0 ("not taken": the matching call would refuse these arguments; mmif_last_error may say why).
  *   name    "mfma<3,2>", "conv1x1_stream", "conv_dma<L1,org1>", "conv_dma<L0,org1,dup>", "thin_async<3>", "thin_wide", "wgrad_dma",
  *           "wgrad_taprow", "wgrad_mfma<3,4>", "wgrad_mfma<1,4,2,2>", "bwd_pair" ("bwd_pair<reg>" under mmif_debug_set_bwd_pair_dma(0)),
- *           "x3" / "valu" (fp32 tensors or impl = VALU: the other fields stay 0)
- *   G       blocks launched; weight gradients: the partial sums per output that the reduce adds (tile groups per channel-group pair)
+ *           fp32 tensors on the split-operand kernels, one name per code object: forward "x3<3,mb2,h16>", "x3<3,mb1,b3,rj4>",
+ *           "x3<3,mb1,b2,nw4,m16>", "x3<1,mb1,h16>" (kernel size, M-block width, operand format h16 | b3 | b2 -- that of
+ *           mmif_get_x3_forward_pieces(): the query sees no operand image --, four-wave / 16-output / four-row variants), input gradient
+ *           "x3_dgrad<3,mb1,nw4>", weight gradient "x3_wgrad<3>", "x3_wgrad<1>", "x3_wgrad_thin<2|4|6>", "x3_wgrad_thin16";
+ *           "valu" (the fp32 FMA kernels: the other fields stay 0)
+ *   G       blocks launched; weight gradients: the partial sums per output that the reduce adds (tile groups per channel-group pair;
+ *           "x3_wgrad<1>": three per tile group)
  *   slices  of that reduce (0: the call has none)
  *   tiles   tiles (x M-blocks where a block owns one; conv1x1_stream: 32-pixel runs) the blocks share out
  *   org     1: the kernel folds the reflect halo itself
- * MMIF_ROUTE_BWD_WIDE: name, tiles and org of its input-gradient half, G and slices of its weight-gradient half (always wgrad_dma). */
+ * MMIF_ROUTE_BWD_WIDE: name, tiles and org of its input-gradient half, G and slices of its weight-gradient half (bf16: always wgrad_dma;
+ * fp32: the x3_wgrad kernel of the layer, leaving its sign map). */
 enum { MMIF_ROUTE_FWD = 0, MMIF_ROUTE_DGRAD = 1, MMIF_ROUTE_DGRAD_ONTO = 2, MMIF_ROUTE_DGRAD_DUP = 3, MMIF_ROUTE_WGRAD = 4, MMIF_ROUTE_BWD_PAIR = 5,
        MMIF_ROUTE_BWD_WIDE = 6 };
 typedef struct {

@@ -30,16 +30,25 @@ size_t bwd_wide_signs_bytes(int n, int cin, int h, int w);
 int bwd_wide(const TV& tx, const TV& tg, const TV& tgx, const void* wpk_dgrad, float* dw, float* db, int cin, int cout, uint64_t mask_bits,
              int accumulate, float* ws, unsigned char* signs, hipStream_t st, int phase);
 // conv_x3.hip
-bool conv_x3_supported(bool dgrad, int ks, int cin, int cout, const TV& tin, const TV& tout);
-int conv_x3(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int cin, int cout, int relu,
-            uint64_t mask_bits, uint64_t accum_bits, hipStream_t st, int ks, const unsigned* signs = nullptr, bool* folded = nullptr);
-bool wgrad_x3_supported(int ks, int cin, int cout, const TV& tx, const TV& tg);
-size_t wgrad_x3_workspace(int cin, int cout, int ks);
-int wgrad_x3(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st, int ks, unsigned* signs = nullptr);
+int x3_image_format(const void* img);   // forward operand format of a packed image (16 | 3 | 2); an address never packed: the process mode
+int conv_x3(const X3Route& r, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int relu, uint64_t mask_bits,
+            uint64_t accum_bits, hipStream_t st, const unsigned* signs = nullptr);
+int wgrad_x3(const X3WgradRoute& r, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st,
+             unsigned* signs = nullptr);
 size_t x3_signs_bytes(int n, int cb, int h, int w);
 }  // namespace mmif
 
 using namespace mmif;
+
+// The split-operand routes of fp32 calls (num_cus <= 0: the device's).  Forward: the format of the operand image given (wpk == NULL, as
+// in mmif_conv2d_route: the process mode); dgrad: tin = gy, tout = gx.  A call without its image (need_image) is not taken.
+static X3Route x3_route(bool dgrad, int ks, int cin, int cout, const TV& tin, const TV& tout, const void* wpk, bool fold, int num_cus = 0) {
+    return x3_conv_route(dgrad, ks, tin, tout, dgrad ? cin : cout, dgrad ? cout : cin, dgrad ? 2 : x3_image_format(wpk), fold,
+                         num_cus > 0 ? num_cus : cached_num_cus(), mmif_get_x3_enabled() != 0);
+}
+static X3WgradRoute x3_wroute(int ks, int cin, int cout, const TV& tx, const TV& tg, int num_cus = 0) {
+    return x3_wgrad_route(ks, cin, cout, tx, tg, num_cus > 0 ? num_cus : cached_num_cus(), mmif_get_x3_enabled() != 0);
+}
 
 // AUTO: bf16 tensors -> the bf16 MFMA kernels, fp32 tensors -> the split-bf16 MFMA kernels (x3_ok: shape covered and, for forward /
 // dgrad, the x3 operand image given), else the fp32 FMA kernels.
@@ -128,10 +137,10 @@ extern "C" int mmif_conv2d_reflect_fwd(const mmif_tensor* x, const float* w, con
     if (int rc = validate_tensor(y, "y")) return rc;
     if (int rc = fwd_check(x, y, cin, cout, ksize)) return rc;
     TV tx = make_tv(x), ty = make_tv(y);
-    const int im = pick_impl(impl, x->dtype, conv_mfma_supported(false, ksize, cin, cout) && w_packed != nullptr, "conv2d_reflect_fwd",
-                             x->dtype == MMIF_F32 && w_packed != nullptr && conv_x3_supported(false, ksize, cin, cout, tx, ty));
+    const X3Route xr = (x->dtype == MMIF_F32 && w_packed != nullptr) ? x3_route(false, ksize, cin, cout, tx, ty, w_packed, false) : X3Route{};
+    const int im = pick_impl(impl, x->dtype, conv_mfma_supported(false, ksize, cin, cout) && w_packed != nullptr, "conv2d_reflect_fwd", xr.mb != 0);
     if (im < 0) return MMIF_EINVAL;
-    if (im == MMIF_IMPL_X3) return conv_x3(false, tx, ty, ty, w_packed, bias, cin, cout, relu, 0, 0, (hipStream_t)stream, ksize);
+    if (im == MMIF_IMPL_X3) return conv_x3(xr, tx, ty, ty, w_packed, bias, relu, 0, 0, (hipStream_t)stream);
     if (im == MMIF_IMPL_MFMA) return conv_mfma(false, ksize, tx, ty, ty, w_packed, bias, cin, cout, relu, 0, 0, (hipStream_t)stream);
     MMIF_REQUIRE(w != nullptr, "conv2d_reflect_fwd: VALU path needs the fp32 master weights");
     return conv_valu(false, x->dtype, ksize, tx, ty, ty, w, bias, cin, cout, relu, 0, 0, (hipStream_t)stream);
@@ -151,8 +160,8 @@ static int dgrad_impl(const char* what, const mmif_tensor* gy, const float* w, c
                      "%s: x does not match gx", what);
         tm = make_tv(x);
     }
-    const int im = pick_impl(impl, gy->dtype, conv_mfma_supported(true, ksize, cin, cout) && w_packed_t != nullptr, what,
-                             gy->dtype == MMIF_F32 && w_packed_t != nullptr && conv_x3_supported(true, ksize, cin, cout, tg, tgx));
+    const X3Route xr = (gy->dtype == MMIF_F32 && w_packed_t != nullptr) ? x3_route(true, ksize, cin, cout, tg, tgx, w_packed_t, fold) : X3Route{};
+    const int im = pick_impl(impl, gy->dtype, conv_mfma_supported(true, ksize, cin, cout) && w_packed_t != nullptr, what, xr.mb != 0);
     if (im < 0) return MMIF_EINVAL;
     bool folded = false;
     int rc;
@@ -166,7 +175,8 @@ static int dgrad_impl(const char* what, const mmif_tensor* gy, const float* w, c
         told = make_tv(gx_old);
     }
     if (im == MMIF_IMPL_X3) {
-        rc = conv_x3(true, tg, tgx, tm, w_packed_t, nullptr, cin, cout, 0, mask_bits, accum_bits, (hipStream_t)stream, ksize, nullptr, fold ? &folded : nullptr);
+        rc = conv_x3(xr, tg, tgx, tm, w_packed_t, nullptr, 0, mask_bits, accum_bits, (hipStream_t)stream);
+        folded = xr.org == 1;
     } else if (im == MMIF_IMPL_MFMA) {
         rc = conv_mfma(true, ksize, tg, tgx, tm, w_packed_t, nullptr, cin, cout, 0, mask_bits, accum_bits, (hipStream_t)stream, fold, &folded,
                        gx_old != nullptr ? &told : nullptr);
@@ -235,7 +245,7 @@ extern "C" int mmif_conv2d_reflect_dgrad_folded_dup(const mmif_tensor* gy, const
 
 extern "C" size_t mmif_conv2d_wgrad_workspace(int32_t cin, int32_t cout, int32_t ksize) {
     size_t a = wgrad_valu_workspace(cin, cout, ksize);
-    const size_t b = wgrad_mfma_workspace(cin, cout, ksize), c = wgrad_x3_workspace(cin, cout, ksize);
+    const size_t b = wgrad_mfma_workspace(cin, cout, ksize), c = x3_wgrad_workspace_bytes(cin, cout, ksize);
     if (b > a) a = b;
     return c > a ? c : a;
 }
@@ -252,10 +262,10 @@ extern "C" int mmif_conv2d_reflect_wgrad(const mmif_tensor* x, const mmif_tensor
         return MMIF_EWORKSPACE;
     }
     TV tx = make_tv(x), tg = make_tv(gy);
-    const int im = pick_impl(impl, x->dtype, wgrad_mfma_supported(ksize, cin, cout), "conv2d_reflect_wgrad",
-                             x->dtype == MMIF_F32 && wgrad_x3_supported(ksize, cin, cout, tx, tg));
+    const X3WgradRoute xw = x->dtype == MMIF_F32 ? x3_wroute(ksize, cin, cout, tx, tg) : X3WgradRoute{};
+    const int im = pick_impl(impl, x->dtype, wgrad_mfma_supported(ksize, cin, cout), "conv2d_reflect_wgrad", xw.kernel != X3WgradRoute::NONE);
     if (im < 0) return MMIF_EINVAL;
-    if (im == MMIF_IMPL_X3) return wgrad_x3(tx, tg, dw, db, cin, cout, accumulate, (float*)workspace, (hipStream_t)stream, ksize);
+    if (im == MMIF_IMPL_X3) return wgrad_x3(xw, tx, tg, dw, db, cin, cout, accumulate, (float*)workspace, (hipStream_t)stream);
     if (im == MMIF_IMPL_MFMA) return wgrad_mfma(ksize, tx, tg, dw, db, cin, cout, accumulate, (float*)workspace, (hipStream_t)stream);
     return wgrad_valu(x->dtype, ksize, tx, tg, dw, db, cin, cout, accumulate, (float*)workspace, (hipStream_t)stream);
 }
@@ -315,9 +325,11 @@ extern "C" int mmif_conv2d_reflect_bwd_wide(const mmif_tensor* gy, const void* w
         MMIF_REQUIRE(gy->n == x->n && gy->h == x->h && gy->w == x->w && gx->n == x->n && gx->h == x->h && gx->w == x->w, "conv2d_reflect_bwd_wide: shape mismatch");
         MMIF_REQUIRE((cin + 7) / 8 == x->cb && x->cb == gx->cb && (cout + 7) / 8 == gy->cb, "conv2d_reflect_bwd_wide: channel blocks do not match");
         const TV tx = make_tv(x), tg = make_tv(gy), tgx = make_tv(gx);
-        MMIF_REQUIRE(wgrad_x3_supported(ksize, cin, cout, tx, tg) && conv_x3_supported(true, ksize, cin, cout, tg, tgx),
+        const X3WgradRoute xw = x3_wroute(ksize, cin, cout, tx, tg);
+        const X3Route xr = x3_route(true, ksize, cin, cout, tg, tgx, w_packed_t, true);
+        MMIF_REQUIRE(xw.kernel != X3WgradRoute::NONE && xr.mb != 0,
                      "conv2d_reflect_bwd_wide: layer %d -> %d k%d / tensors not covered by the split-operand kernels", cin, cout, ksize);
-        if (workspace == nullptr || workspace_bytes < wgrad_x3_workspace(cin, cout, ksize)) {
+        if (workspace == nullptr || workspace_bytes < x3_wgrad_workspace_bytes(cin, cout, ksize)) {
             set_error("conv2d_reflect_bwd_wide: workspace too small");
             return MMIF_EWORKSPACE;
         }
@@ -326,11 +338,10 @@ extern "C" int mmif_conv2d_reflect_bwd_wide(const mmif_tensor* gy, const void* w
             return MMIF_EWORKSPACE;
         }
         if (phase != 2)
-            if (int rc = wgrad_x3(tx, tg, dw, db, cin, cout, accumulate, (float*)workspace, (hipStream_t)stream, ksize, (unsigned*)signs)) return rc;
+            if (int rc = wgrad_x3(xw, tx, tg, dw, db, cin, cout, accumulate, (float*)workspace, (hipStream_t)stream, (unsigned*)signs)) return rc;
         if (phase == 1) return MMIF_OK;
-        bool folded = false;
-        if (int rc = conv_x3(true, tg, tgx, tx, w_packed_t, nullptr, cin, cout, 0, mask_bits, 0, (hipStream_t)stream, ksize, (const unsigned*)signs, &folded)) return rc;
-        return (ksize == 1 || folded) ? MMIF_OK : mmif_fold_halo(gx, stream);
+        if (int rc = conv_x3(xr, tg, tgx, tx, w_packed_t, nullptr, 0, mask_bits, 0, (hipStream_t)stream, (const unsigned*)signs)) return rc;
+        return (ksize == 1 || xr.org == 1) ? MMIF_OK : mmif_fold_halo(gx, stream);
     }
     if (int rc = wide_check(gy, x, cin, cout, ksize)) return rc;
     MMIF_REQUIRE(w_packed_t != nullptr && dw != nullptr, "conv2d_reflect_bwd_wide: NULL operand image / dw");
@@ -368,25 +379,30 @@ extern "C" int mmif_conv2d_route(int32_t op, const mmif_tensor* a, const mmif_te
     const bool f32 = a->dtype == MMIF_F32;
     const bool dgrad = op == MMIF_ROUTE_DGRAD || op == MMIF_ROUTE_DGRAD_ONTO || op == MMIF_ROUTE_DGRAD_DUP;
     int im;
+    X3Route xr{};
+    X3WgradRoute xw{};
     if (op == MMIF_ROUTE_FWD) {
         if (fwd_check(a, b, cin, cout, ksize) != MMIF_OK) return 0;
-        im = pick_impl(impl, a->dtype, conv_mfma_supported(false, ksize, cin, cout), "conv2d_route", f32 && conv_x3_supported(false, ksize, cin, cout, ta, tb));
+        if (f32) xr = x3_route(false, ksize, cin, cout, ta, tb, nullptr, false, num_cus);
+        im = pick_impl(impl, a->dtype, conv_mfma_supported(false, ksize, cin, cout), "conv2d_route", xr.mb != 0);
     } else if (dgrad) {
         if (dgrad_check("conv2d_route", a, b, cin, cout, ksize) != MMIF_OK) return 0;
         if (op != MMIF_ROUTE_DGRAD && !folded_bf16_pair(a, b)) return 0;
-        im = op != MMIF_ROUTE_DGRAD ? MMIF_IMPL_MFMA
-                                    : pick_impl(impl, a->dtype, conv_mfma_supported(true, ksize, cin, cout), "conv2d_route",
-                                                f32 && conv_x3_supported(true, ksize, cin, cout, ta, tb));
+        if (f32 && op == MMIF_ROUTE_DGRAD) xr = x3_route(true, ksize, cin, cout, ta, tb, nullptr, fold != 0, num_cus);
+        im = op != MMIF_ROUTE_DGRAD ? MMIF_IMPL_MFMA : pick_impl(impl, a->dtype, conv_mfma_supported(true, ksize, cin, cout), "conv2d_route", xr.mb != 0);
     } else if (op == MMIF_ROUTE_WGRAD) {
         if (wgrad_check(a, b, cin, cout, ksize) != MMIF_OK) return 0;
-        im = pick_impl(impl, a->dtype, wgrad_mfma_supported(ksize, cin, cout), "conv2d_route", f32 && wgrad_x3_supported(ksize, cin, cout, ta, tb));
+        if (f32) xw = x3_wroute(ksize, cin, cout, ta, tb, num_cus);
+        im = pick_impl(impl, a->dtype, wgrad_mfma_supported(ksize, cin, cout), "conv2d_route", xw.kernel != X3WgradRoute::NONE);
     } else if (op == MMIF_ROUTE_BWD_PAIR) {
         if (pair_check(b, a, cin, cout, ksize) != MMIF_OK) return 0;
         im = MMIF_IMPL_MFMA;
     } else if (op == MMIF_ROUTE_BWD_WIDE) {
         if (f32 && b->dtype == MMIF_F32) {   // fp32 tensors: the split-operand pair of kernels, where they take the layer
+            xw = x3_wroute(ksize, cin, cout, ta, tb, num_cus);
+            xr = x3_route(true, ksize, cin, cout, tb, halo1_like(ta), nullptr, true, num_cus);
             if (!(a->halo == 0 && a->n == b->n && a->h == b->h && a->w == b->w && (cin + 7) / 8 == a->cb && (cout + 7) / 8 == b->cb &&
-                  wgrad_x3_supported(ksize, cin, cout, ta, tb) && conv_x3_supported(true, ksize, cin, cout, tb, halo1_like(ta))))
+                  xw.kernel != X3WgradRoute::NONE && xr.mb != 0))
                 return 0;
             im = MMIF_IMPL_X3;
         } else {
@@ -398,8 +414,20 @@ extern "C" int mmif_conv2d_route(int32_t op, const mmif_tensor* a, const mmif_te
         return 0;
     }
     if (im < 0) return 0;
+    if (im == MMIF_IMPL_X3) {   // (bwd_wide: name, tiles and org of its input-gradient half, G and slices of its weight-gradient half)
+        if (xw.kernel != X3WgradRoute::NONE) {
+            route_name(xw, out->name, sizeof(out->name));
+            out->G = xw.red_G; out->slices = xw.slices; out->tiles = xw.total;
+        }
+        if (xr.mb != 0) {
+            route_name(xr, out->name, sizeof(out->name));
+            out->tiles = xr.total; out->org = xr.org;
+            if (xw.kernel == X3WgradRoute::NONE) out->G = xr.G;
+        }
+        return 1;
+    }
     if (im != MMIF_IMPL_MFMA) {
-        snprintf(out->name, sizeof(out->name), "%s", im == MMIF_IMPL_X3 ? "x3" : "valu");
+        snprintf(out->name, sizeof(out->name), "valu");
         return 1;
     }
     if (num_cus <= 0) num_cus = cached_num_cus();

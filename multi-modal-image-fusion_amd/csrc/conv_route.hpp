@@ -1,6 +1,7 @@
-// Which kernel a bf16 ConvLayer call launches, and on what grid: decided ONCE, here, by pure host functions of the call's geometry.
+// Which kernel a ConvLayer call launches, and on what grid: decided ONCE, here, by pure host functions of the call's geometry -- the bf16
+// families and the fp32 split-operand ("x3") family.
 //
-// conv_mfma.hip / conv1x1.hip / enc_wgrad.hip launch what a route says and nothing else; the `_supported` queries and
+// conv_mfma.hip / conv1x1.hip / enc_wgrad.hip / conv_x3.hip launch what a route says and nothing else; the `_supported` queries and
 // mmif_conv2d_route (csrc/conv_api.hip) ask the same functions, so the tests and the engines see what the dispatch does.  No HIP runtime
 // call in this header: the compute-unit count and the switches are arguments (the same arguments give the same route).
 #pragma once
@@ -29,6 +30,13 @@ constexpr size_t C1_MAX_LDS = 128 * 1024;
 constexpr int c1_waves_per_eu(int nmt) { return nmt <= 4 ? 4 : (nmt <= 8 ? 3 : 2); }   // by 16-row fragments of the output
 inline size_t c1_lds_bytes(int nch, int m16p) { return (size_t)nch * 4 * m16p * 16 + (size_t)m16p * 4; }
 constexpr int BP_MAXG = 512;   // blocks of bwd_pair_kernel
+// the split-operand family (csrc/conv_x3.hip); the thin / dense partials' sizes XT_PER / XD_PER are in wgrad_reduce.hpp
+constexpr int X3_TW = 32;                        // conv_x3_kernel: output tile columns; rows = 2 per wave (16 with 8 waves, 8 with 4)
+constexpr int XW_TW = 16;                        // wgrad_x3_kernel: pixel-tile columns = the 16 pixels of one k-step
+constexpr int XT_TH = 8, XT_TW = 16;             // wgrad_x3_thin_kernel / wgrad_x3_dense_kernel: pixel tile
+__host__ __device__ constexpr int x3_mb(int n_out) { return n_out > 32 ? 2 : 1; }
+inline int x3_nmb(int n_out) { return cdiv(n_out, 32 * x3_mb(n_out)); }
+inline int x3_nch(int n_in) { return cdiv(cdiv(n_in, 8), 2); }
 
 inline int pick_mf(int n_out) {
     const int fr = (n_out + 15) / 16;
@@ -246,6 +254,113 @@ inline PairRoute pair_route(int ks, int cin, int cout, const TV& tx, const TV& t
     return r;
 }
 
+// ---------------------------------------------------------------- fp32 tensors: the split-operand ("x3") family (csrc/conv_x3.hip)
+// The forward operand format (16 | 3 | 2, csrc/conv_x3.hip; dgrad: always 2) and $MMIF_X3 (`enabled`) are arguments like the compute units.
+struct X3Route {
+    int mb;                          // 0: not taken; else conv_x3_kernel<mb, dgrad, np, nw, rj, ks, f16, m16>
+    int np, nw, rj, ks;
+    bool f16, m16, dgrad;
+    int org;                         // 1: interior tiles + in-tile fold steps, the halo ring stays untouched (zero: the fold-me call's contract)
+    int n_out, nch, nmb;             // output channels, input chunks, M-blocks
+    int tiles_x, tpi, total;         // 32 x (rj nw) tiles: per row, per image, in all
+    int G;                           // persistent blocks
+};
+inline bool x3_grad_ok(const TV& t) { return t.halo == 0 || (t.halo == 1 && t.folded); }
+inline bool x3_small(const TV& t) { return t.plane * 32 * 8 < (1ll << 32); }   // 8 planes addressed with 32-bit byte offsets
+// forward: tin = x, tout = y;  dgrad: tin = gy (halo 0 or folded halo 1), tout = gx (the padded domain is written unless org = 1);
+// want_fold (dgrad): the caller wants fold_halo(gx) applied and guarantees a zero halo ring on entry -- org says whether the kernel does it
+inline X3Route x3_conv_route(bool dgrad, int ks, const TV& tin, const TV& tout, int n_out, int n_in, int fmt, bool want_fold, int num_cus, bool enabled) {
+    X3Route r{};
+    if (!enabled || (ks != 3 && ks != 1) || n_in < 1 || n_out < 1 || (dgrad && !x3_grad_ok(tin))) return r;
+    if (n_out > 64 * 8) return r;   // mask / accum bits address 64 channel blocks
+    if (!(ks == 1 || (tin.h >= 2 && tin.w >= 2)) || !x3_small(tin) || !x3_small(tout)) return r;
+    const bool six = !dgrad && fmt == 3;
+    r.mb = x3_mb(n_out); r.np = six ? 3 : 2; r.nw = 8; r.rj = 2; r.ks = ks;
+    r.f16 = !dgrad && fmt == 16; r.dgrad = dgrad;
+    if (ks == 3 && r.mb == 1) {
+        // thin layers (<= 32 out, <= 64 in: the DenseBlock convs and the decoder's tail) have almost no MFMA work per tile and run at the
+        // latency of ONE tile's loads per block: four-wave blocks (8-row tiles, 16-channel chunks, 42 KB of LDS, 146 VGPRs) put THREE
+        // independent blocks on a CU: forward 16->16 102 -> 77 us, 32->16 161 -> 144, 48->16 258 -> 212, 64->32 348 -> 324; dgrad 16->16
+        // 160 -> 123, 32->16 204 -> 175 (two blocks: half of that; four: over-subscribed, slower; the 64-out-channel kernels on four-wave
+        // blocks: +-0).  <= 16 output channels: 16 x 16 x 32 MFMAs, K = two taps x 16 channels (no padded half tile)
+        if (n_in <= 64 && !six) { r.nw = 4; r.m16 = n_out <= 16; }
+        // one 32-channel accumulator tile per pixel row, so a wave takes FOUR rows (32 x 32 pixel tiles) in the 3-piece forward: the same
+        // 216 MFMAs per wave and barrier as the 64-channel kernels for half the weight staging
+        else if (six) r.rj = 4;
+    }
+    r.org = (dgrad && ks == 3 && !r.m16 && want_fold && tout.halo == 1 && tout.h >= 4 && tout.w >= 4) ? 1 : 0;
+    r.n_out = n_out; r.nch = x3_nch(n_in); r.nmb = x3_nmb(n_out);
+    r.tiles_x = cdiv(tout.ws - 2 * r.org, X3_TW);
+    r.tpi = r.tiles_x * cdiv(tout.hs - 2 * r.org, r.rj * r.nw);
+    r.total = r.tpi * tout.n;
+    r.G = num_cus * (r.nw == 4 ? 3 : 1);   // four-wave blocks: three per CU (42 KB of LDS, < 168 VGPRs each; two: half the gain; four: over-subscribed)
+    if (r.total < r.G) r.G = r.total;
+    return r;
+}
+
+// Tile groups per 64 x 64 channel pair of wgrad_x3_kernel: about one persistent block per CU in total, never more than the workspace holds
+inline int x3_wgrad_pairs(int cin, int cout) { return cdiv(cin, 64) * cdiv(cout, 64); }
+inline int x3_wgrad_G_max(int cin, int cout) {   // a gfx950 part has at most 256 CUs
+    const int G = 256 / x3_wgrad_pairs(cin, cout);
+    return G < 1 ? 1 : G;
+}
+inline int x3_wgrad_G(int cin, int cout, int num_cus) {
+    int G = num_cus / x3_wgrad_pairs(cin, cout);
+    if (G >= 8) G &= ~7;
+    if (G > x3_wgrad_G_max(cin, cout)) G = x3_wgrad_G_max(cin, cout);
+    return G < 1 ? 1 : G;
+}
+inline size_t x3_wgrad_workspace_bytes(int cin, int cout, int ks) {   // (1x1: three k-split partials per block)
+    if (ks != 1 && ks != 3) return 0;
+    return (size_t)(ks == 1 ? 3 : 1) * x3_wgrad_G_max(cin, cout) * x3_wgrad_pairs(cin, cout) * wgrad_x3_reduce::per(ks * ks) * sizeof(float);
+}
+constexpr int XD_MAXG = 512;   // wgrad_x3_dense_kernel: two blocks per CU
+inline int x3_dense_G(int total, int num_cus) {
+    const int G = 2 * num_cus < XD_MAXG ? 2 * num_cus : XD_MAXG;
+    return total < G ? total : G;
+}
+
+struct X3WgradRoute {
+    enum Kernel { NONE, K1, THIN, THIN16, WIDE } kernel;   // wgrad_x3_kernel<8,8,8,1>, wgrad_x3_thin_kernel<nxc>, wgrad_x3_kernel<16,6,2,3> / <8,8,8,3>
+    int nxc;                      // THIN: input channel blocks staged (2 | 4 | 6)
+    int tiles_x, tpi, total;      // 8 x 16 pixel tiles (THIN16: 16 x 16): per row, per image, in all
+    int n_icg, n_ocg;             // 64 x 64 channel groups; the grid is G * n_icg * n_ocg blocks (THIN: one group)
+    int G;                        // tile groups launched per channel-group pair
+    int red_G, slices;            // partials the reduce sums (1x1: three per block) and its slices
+};
+inline X3WgradRoute x3_wgrad_route(int ks, int cin, int cout, const TV& tx, const TV& tg, int num_cus, bool enabled) {
+    X3WgradRoute r{};
+    if (!enabled || (ks != 3 && ks != 1) || cin < 1 || cout < 1 || !x3_grad_ok(tg) || tx.halo != 0) return r;
+    if (!(ks == 1 || (tx.h >= 2 && tx.w >= 2)) || !x3_small(tx) || !x3_small(tg)) return r;
+    const bool thin = ks == 3 && cin <= 48 && cout <= 16;
+    auto tiles = [&](int th, int tw) {
+        r.tiles_x = cdiv(tx.w, tw);
+        r.tpi = r.tiles_x * cdiv(tx.h, th);
+        r.total = r.tpi * tx.n;
+    };
+    r.n_icg = r.n_ocg = 1;
+    if (thin) {
+        tiles(XT_TH, XT_TW);
+        r.G = num_cus * (cin <= 16 ? 5 : (cin <= 32 ? 4 : 3));   // blocks per CU: what the registers (92 / 128 / 168) and the LDS (20 / 32 / 44 KB) allow
+        if (r.total < r.G) r.G = r.total;
+        if ((size_t)r.G * XT_PER * sizeof(float) <= x3_wgrad_workspace_bytes(cin, cout, 3)) {
+            r.kernel = X3WgradRoute::THIN;
+            r.nxc = cin <= 16 ? 2 : (cin <= 32 ? 4 : 6);
+            r.red_G = r.G;
+            r.slices = red_slices<wgrad_x3_thin_reduce>(r.red_G);
+            return r;
+        }
+    }
+    r.kernel = ks == 1 ? X3WgradRoute::K1 : (thin ? X3WgradRoute::THIN16 : X3WgradRoute::WIDE);
+    tiles(thin ? 16 : 8, XW_TW);
+    r.n_icg = cdiv(cin, 64); r.n_ocg = cdiv(cout, 64);
+    r.G = x3_wgrad_G(cin, cout, num_cus);
+    if (r.total < r.G) r.G = r.total;
+    r.red_G = ks == 1 ? 3 * r.G : r.G;
+    r.slices = red_slices<wgrad_x3_reduce>(r.red_G);
+    return r;
+}
+
 // ---------------------------------------------------------------- names (tests/conv_cases.py REQUIRED_LABELS)
 inline void route_name(const ConvRoute& r, char* s, size_t n) {
     switch (r.kernel) {
@@ -265,6 +380,20 @@ inline void route_name(const WgradRoute& r, char* s, size_t n) {
             if (r.ks == 1 && r.mfw == 4) snprintf(s, n, "wgrad_mfma<1,4,%d,%d>", r.ksplit, r.icf);
             else snprintf(s, n, "wgrad_mfma<%d,%d>", r.ks, r.mfw);
             break;
+        default: snprintf(s, n, "none"); break;
+    }
+}
+inline void route_name(const X3Route& r, char* s, size_t n) {   // one per code object: "x3<3,mb1,h16,nw4,m16>", "x3_dgrad<1,mb2>"
+    if (r.mb == 0) { snprintf(s, n, "none"); return; }
+    const char* fmt = r.dgrad ? "" : (r.f16 ? ",h16" : (r.np == 3 ? ",b3" : ",b2"));   // (the input gradient always reads two bf16 pieces)
+    snprintf(s, n, "x3%s<%d,mb%d%s%s%s%s>", r.dgrad ? "_dgrad" : "", r.ks, r.mb, fmt, r.nw == 4 ? ",nw4" : "", r.m16 ? ",m16" : "", r.rj == 4 ? ",rj4" : "");
+}
+inline void route_name(const X3WgradRoute& r, char* s, size_t n) {
+    switch (r.kernel) {
+        case X3WgradRoute::K1: snprintf(s, n, "x3_wgrad<1>"); break;
+        case X3WgradRoute::THIN: snprintf(s, n, "x3_wgrad_thin<%d>", r.nxc); break;
+        case X3WgradRoute::THIN16: snprintf(s, n, "x3_wgrad_thin16"); break;
+        case X3WgradRoute::WIDE: snprintf(s, n, "x3_wgrad<3>"); break;
         default: snprintf(s, n, "none"); break;
     }
 }

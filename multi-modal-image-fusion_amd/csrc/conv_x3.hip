@@ -27,7 +27,7 @@
 //   pixel-major hi / lo tiles with the LDS transpose read (ds_read_b64_tr_b16), 16 pixels of one tile row per k-step.  It can leave the
 //   ReLU sign map of x for the dgrad that follows (mmif_conv2d_reflect_bwd_wide).
 // wgrad_x3_thin_kernel: the same for <= 48 input / <= 16 output channels: four-wave blocks, 3-5 per CU, 16x16x32 MFMAs.
-#include "wgrad_reduce.hpp"
+#include "conv_route.hpp"
 #include <stdlib.h>
 #include <mutex>
 #include <unordered_map>
@@ -41,11 +41,7 @@ typedef __attribute__((ext_vector_type(4))) float x3_f4;        // native vector
 typedef __attribute__((ext_vector_type(4))) unsigned x3_u4;     // travel through the staging lambdas were left in scratch / promoted to LDS
 #define X3_LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 
-constexpr int X3_TW = 32;                        // output tile columns; rows = 2 per wave (16 with 8 waves, 8 with 4)
-
-__host__ __device__ constexpr int x3_mb(int n_out) { return n_out > 32 ? 2 : 1; }
-static inline int x3_nmb(int n_out) { return cdiv(n_out, 32 * x3_mb(n_out)); }
-static inline int x3_nch(int n_in) { return cdiv(cdiv(n_in, 8), 2); }
+// (tile geometry shared with the routes -- X3_TW, XW_TW, XT_TH / XT_TW, x3_mb / x3_nmb / x3_nch: csrc/conv_route.hpp)
 // operand image: [m-block][chunk][hi | lo][tap u*3+v][channel block 0 / 1 of the chunk][32*MB out channels][8 in channels] bf16
 static size_t x3_packed_bytes(int n_out, int n_in, int pieces, int ks = 3) {
     return (size_t)x3_nmb(n_out) * x3_nch(n_in) * pieces * ks * ks * 2 * 32 * x3_mb(n_out) * 16;
@@ -729,7 +725,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_x3_kernel(TV tin, TV tout, TV
 
 
 // ------------------------------------------------------------------ wgrad
-constexpr int XW_TW = 16;                        // pixel-tile columns = the 16 pixels of one k-step
 constexpr int XW_THREADS = 768;                  // (the 12-wave instantiations; wgrad_x3_kernel's NWV)
 
 // TH x 16 pixel tiles, NXC / NGC channel blocks of the activation / gradient group kept in LDS.  <8, 8, 8>: the general 64 x 64 channel
@@ -1013,7 +1008,7 @@ __global__ __launch_bounds__(64 * NWV, 12 / NWV) void wgrad_x3_kernel(TV tx, TV 
 // kernels: the blocks hide each other's load latency --, 16 x 16 x 32 MFMAs (no padding: M = 16 output channels, N = 16 input channels,
 // K = the 32 pixels of two tile rows) and the same two-piece products.  Work item (j, v) = input-channel block j x tap column v: it owns
 // dW[16][16 j .. 16 j + 15][u = 0..2][v] in 12 accumulator registers; a wave takes items wave, wave + 4, ...
-constexpr int XT_TH = 8, XT_TW = 16, XT_XH = XT_TH + 2, XT_XW = XT_TW + 2;
+constexpr int XT_XH = XT_TH + 2, XT_XW = XT_TW + 2;
 constexpr int XT_XPL = XT_XH * XT_XW, XT_GPL = XT_TH * XT_TW + 4;        // 180 / 132 granules per plane: both = 4 mod 16, so that the two planes a 32-lane
                                                                          // group of the transposing read touches fall on disjoint bank halves (184 was 2-way: 35 % extra cycles)
 constexpr int XT_THREADS = 256;
@@ -1356,18 +1351,6 @@ __global__ __launch_bounds__(XT_THREADS, 2) void wgrad_x3_dense_kernel(TV tx, TV
 }
 
 // ------------------------------------------------------------------ host side
-static int x3_num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-        if (const char* e = getenv("MMIF_NUM_CUS")) n = atoi(e) > 0 ? atoi(e) : n;   // (experiments: persistent grids on part of the chip)
-    }
-    return n;
-}
-
 static bool x3_enabled() {   // $MMIF_X3=0: fp32 tensors stay on the fp32 FMA kernels (A/B timing, cross-checks)
     static int on = -1;
     if (on < 0) {
@@ -1375,16 +1358,6 @@ static bool x3_enabled() {   // $MMIF_X3=0: fp32 tensors stay on the fp32 FMA ke
         on = (e != nullptr && e[0] == '0') ? 0 : 1;
     }
     return on == 1;
-}
-
-static bool x3_grad_ok(const TV& t) { return t.halo == 0 || (t.halo == 1 && t.folded); }
-static bool x3_small(const TV& t) { return t.plane * 32 * 8 < (1ll << 32); }   // 8 planes addressed with 32-bit byte offsets
-
-bool conv_x3_supported(bool dgrad, int ks, int cin, int cout, const TV& tin, const TV& tout) {
-    if (!x3_enabled() || (ks != 3 && ks != 1) || cin < 1 || cout < 1) return false;
-    if (dgrad && !x3_grad_ok(tin)) return false;
-    if ((dgrad ? cin : cout) > 64 * 8) return false;   // mask / accum bits address 64 channel blocks
-    return (ks == 1 || (tin.h >= 2 && tin.w >= 2)) && x3_small(tin) && x3_small(tout);
 }
 
 // operand format of the FORWARD pass: 16 (default) = two SCALED FP16 pieces, 3 products, fp32-grade (2^-23 per product); 3 = three bf16
@@ -1412,7 +1385,7 @@ static void x3_note_format(const void* img, int pieces) {
     std::lock_guard<std::mutex> lk(g_fmt_mu);
     g_fwd_fmt[img] = pieces;
 }
-static int x3_image_format(const void* img) {
+int x3_image_format(const void* img) {
     std::lock_guard<std::mutex> lk(g_fmt_mu);
     auto it = g_fwd_fmt.find(img);
     return it != g_fwd_fmt.end() ? it->second : x3_fwd_pieces();
@@ -1455,164 +1428,74 @@ int conv_x3_pack_multi(const mmif_pack_job* jobs, int n_jobs, hipStream_t st) {
 }
 
 template <int MB, int NP, int NW, int RJ, int KS = 3, bool F16 = false, bool M16 = false>
-static int launch_conv_x3(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int n_out, int n_in,
-                          int relu, uint64_t mask_bits, uint64_t accum_bits, hipStream_t st, const unsigned* signs, bool* folded = nullptr) {
-    // dgrad, 3x3, the 32 x 32 x 16 tiles, a caller that wants the fold (folded != nullptr) and an output whose fold targets are distinct:
-    // interior tiles + in-tile fold steps (org = 1), the halo ring stays untouched (zero: the caller's contract for a fold-me call)
-    const int org = (dgrad && KS == 3 && !M16 && RJ <= 2 && folded != nullptr && tout.halo == 1 && tout.h >= 4 && tout.w >= 4) ? 1 : 0;
-    if (org) *folded = true;
-    const int tiles_x = cdiv(tout.ws - 2 * org, X3_TW), tiles_y = cdiv(tout.hs - 2 * org, RJ * NW);
-    const int tpi = tiles_x * tiles_y, total = tpi * tout.n;
-    constexpr int nw4_blocks = 3;   // four-wave blocks per CU (persistent grid): 42 KB of LDS, < 168 VGPRs each (two: half the gain; four: over-subscribed)
-    int G = x3_num_cus() * (NW == 4 ? nw4_blocks : 1);
-    if (total < G) G = total;
-    const int nch = x3_nch(n_in), nmb = x3_nmb(n_out);
+static int launch_conv_x3(const X3Route& r, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int relu, uint64_t mask_bits,
+                          uint64_t accum_bits, hipStream_t st, const unsigned* signs) {
     constexpr int X3_THREADS = 64 * NW;
     static int abl = -1;
     if (abl < 0) abl = ablate_env("x3");
     relu = (relu & 255) | (abl << 8);
-    if (dgrad)
-        hipLaunchKernelGGL((conv_x3_kernel<MB, true, NP, NW, RJ, KS, false, M16>), dim3(G), dim3(X3_THREADS), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, n_out, nch, nmb,
-                           relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, tiles_x, tpi, total, signs, org);
+    if (r.dgrad)
+        hipLaunchKernelGGL((conv_x3_kernel<MB, true, NP, NW, RJ, KS, false, M16>), dim3(r.G), dim3(X3_THREADS), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, r.n_out, r.nch, r.nmb,
+                           relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, r.tiles_x, r.tpi, r.total, signs, r.org);
     else
-        hipLaunchKernelGGL((conv_x3_kernel<MB, false, NP, NW, RJ, KS, F16, M16>), dim3(G), dim3(X3_THREADS), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, n_out, nch, nmb,
-                           relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, tiles_x, tpi, total, (const unsigned*)nullptr, 0);
-    return check_launch(dgrad ? "conv_x3 dgrad" : "conv_x3 fwd");
+        hipLaunchKernelGGL((conv_x3_kernel<MB, false, NP, NW, RJ, KS, F16, M16>), dim3(r.G), dim3(X3_THREADS), 0, st, tin, tout, tmask, (const uint4*)wpk, bias, r.n_out, r.nch, r.nmb,
+                           relu, (unsigned long long)mask_bits, (unsigned long long)accum_bits, r.tiles_x, r.tpi, r.total, (const unsigned*)nullptr, 0);
+    return check_launch(r.dgrad ? "conv_x3 dgrad" : "conv_x3 fwd");
 }
 
-// forward: tin = x, tout = y;  dgrad: tin = gy (halo 0 or folded halo 1), tout = gx (the padded domain is written; the caller folds)
-// folded (dgrad): non-NULL = the caller wants fold_halo(gx) applied and guarantees a zero halo ring on entry; *folded says whether the kernel
-// chosen did it (interior tiles + fold steps) -- otherwise the caller runs the fold kernel
-int conv_x3(bool dgrad, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int cin, int cout, int relu,
-            uint64_t mask_bits, uint64_t accum_bits, hipStream_t st, int ks, const unsigned* signs, bool* folded) {
-    if (folded != nullptr) *folded = false;
-    const int n_out = dgrad ? cin : cout, n_in = dgrad ? cout : cin;
-    const int fmt = dgrad ? 2 : x3_image_format(wpk);
-    const bool six = !dgrad && fmt == 3, h16 = !dgrad && fmt == 16;
-#define X3_ARGS tin, tout, tmask, wpk, bias, n_out, n_in, relu, mask_bits, accum_bits, st, signs, folded
-    if (ks == 1) {
-        if (x3_mb(n_out) == 2) {
-            if (h16) return launch_conv_x3<2, 2, 8, 2, 1, true>(false, X3_ARGS);
-            return six ? launch_conv_x3<2, 3, 8, 2, 1>(false, X3_ARGS) : launch_conv_x3<2, 2, 8, 2, 1>(dgrad, X3_ARGS);
-        }
-        if (h16) return launch_conv_x3<1, 2, 8, 2, 1, true>(false, X3_ARGS);
-        return six ? launch_conv_x3<1, 3, 8, 2, 1>(false, X3_ARGS) : launch_conv_x3<1, 2, 8, 2, 1>(dgrad, X3_ARGS);
-    }
-    if (x3_mb(n_out) == 2) {
-        if (h16) return launch_conv_x3<2, 2, 8, 2, 3, true>(false, X3_ARGS);
-        return six ? launch_conv_x3<2, 3, 8, 2>(false, X3_ARGS) : launch_conv_x3<2, 2, 8, 2>(dgrad, X3_ARGS);
-    }
-    // <= 32 output channels: one 32-channel accumulator tile per pixel row, so a wave takes FOUR rows (32 x 32 pixel tiles) in the
-    // 3-piece forward: the same 216 MFMAs per wave and barrier as the 64-channel kernels for half the weight staging
-    constexpr int rj4 = 1;
-    // thin layers (<= 32 out, <= 64 in: the DenseBlock convs and the decoder's tail) have almost no MFMA work per tile and run at the
-    // latency of ONE tile's loads per block: four-wave blocks (8-row tiles, 16-channel chunks, 42 KB of LDS, 146 VGPRs) put THREE
-    // independent blocks on a CU: forward 16->16 102 -> 77 us, 32->16 161 -> 144, 48->16 258 -> 212, 64->32 348 -> 324; dgrad 16->16
-    // 160 -> 123, 32->16 204 -> 175 (two blocks: half of that; four: over-subscribed, slower; the 64-out-channel kernels on four-wave
-    // blocks: +-0)
-    if (n_in <= 64 && !six) {
-        if (n_out <= 16) {      // <= 16 output channels: 16 x 16 x 32 MFMAs, K = two taps x 16 channels (no padded half tile)
-            if (h16) return launch_conv_x3<1, 2, 4, 2, 3, true, true>(false, X3_ARGS);
-            return launch_conv_x3<1, 2, 4, 2, 3, false, true>(dgrad, X3_ARGS);
-        }
-        if (h16) return launch_conv_x3<1, 2, 4, 2, 3, true>(false, X3_ARGS);
-        return launch_conv_x3<1, 2, 4, 2>(dgrad, X3_ARGS);
-    }
-    if (h16) return launch_conv_x3<1, 2, 8, 2, 3, true>(false, X3_ARGS);
-    if (six) return rj4 ? launch_conv_x3<1, 3, 8, 4>(false, X3_ARGS) : launch_conv_x3<1, 3, 8, 2>(false, X3_ARGS);
-    return launch_conv_x3<1, 2, 8, 2>(dgrad, X3_ARGS);
-#undef X3_ARGS
-}
-
-bool wgrad_x3_supported(int ks, int cin, int cout, const TV& tx, const TV& tg) {
-    return x3_enabled() && (ks == 3 || ks == 1) && cin >= 1 && cout >= 1 && x3_grad_ok(tg) && tx.halo == 0 && (ks == 1 || (tx.h >= 2 && tx.w >= 2)) && x3_small(tx) && x3_small(tg);
-}
-
-static int wgrad_x3_G(int cin, int cout) {
-    const int npairs = cdiv(cin, 64) * cdiv(cout, 64);
-    int G = x3_num_cus() / npairs;
-    if (G >= 8) G &= ~7;
-    return G < 1 ? 1 : G;
-}
-
-size_t wgrad_x3_workspace(int cin, int cout, int ks) {
-    if (ks == 1) {   // three k-split partials per block
-        const size_t npairs = (size_t)cdiv(cin, 64) * cdiv(cout, 64);
-        size_t G = 256 / npairs;
-        if (G < 1) G = 1;
-        const size_t dyn = (size_t)wgrad_x3_G(cin, cout);
-        if (dyn > G) G = dyn;
-        return 3 * G * npairs * wgrad_x3_reduce::per(1) * sizeof(float);
-    }
-    if (ks != 3) return 0;
-    const size_t npairs = (size_t)cdiv(cin, 64) * cdiv(cout, 64);
-    size_t G = 256 / npairs;   // upper bound of wgrad_x3_G on any gfx950 part (<= 256 CUs) without asking the device
-    if (G < 1) G = 1;
-    const size_t dyn = (size_t)wgrad_x3_G(cin, cout);
-    if (dyn > G) G = dyn;
-    return G * npairs * wgrad_x3_reduce::per(9) * sizeof(float);
+// launches what the route says (x3_conv_route, csrc/conv_route.hpp; forward: its fmt = x3_image_format(wpk)).  dgrad with r.org == 0 writes
+// the padded domain: a caller that wants the fold runs the fold kernel
+int conv_x3(const X3Route& r, const TV& tin, const TV& tout, const TV& tmask, const void* wpk, const float* bias, int relu, uint64_t mask_bits,
+            uint64_t accum_bits, hipStream_t st, const unsigned* signs) {
+#define X3_GO(MB, NP, NW, RJ, KS, F16, M16)                                                                                 \
+    if (r.mb == MB && r.np == NP && r.nw == NW && r.rj == RJ && r.ks == KS && r.f16 == F16 && r.m16 == M16) \
+        return launch_conv_x3<MB, NP, NW, RJ, KS, F16, M16>(r, tin, tout, tmask, wpk, bias, relu, mask_bits, accum_bits, st, signs)
+#define X3_GO_FMT(MB, KS) X3_GO(MB, 2, 8, 2, KS, true, false); X3_GO(MB, 3, 8, 2, KS, false, false); X3_GO(MB, 2, 8, 2, KS, false, false)
+    X3_GO_FMT(2, 1); X3_GO_FMT(1, 1); X3_GO_FMT(2, 3); X3_GO_FMT(1, 3);   // eight waves, two rows each: every format (<1, 3, 8, 2, 3>: rj = 2 of the 3-piece forward, A/B only)
+    X3_GO(1, 3, 8, 4, 3, false, false);
+    X3_GO(1, 2, 4, 2, 3, true, true); X3_GO(1, 2, 4, 2, 3, false, true); X3_GO(1, 2, 4, 2, 3, true, false); X3_GO(1, 2, 4, 2, 3, false, false);
+#undef X3_GO_FMT
+#undef X3_GO
+    set_error("conv_x3: no kernel for this route");
+    return MMIF_EINVAL;
 }
 
 size_t x3_signs_bytes(int n, int cb, int h, int w) { return (size_t)n * ((cb + 3) / 4) * h * w * 4; }
 
-int wgrad_x3(const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st, int ks, unsigned* signs) {
-    if (ks == 1) {
-        const int tiles_x = cdiv(tx.w, XW_TW), tiles_y = cdiv(tx.h, 8);
-        const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-        const int n_icg = cdiv(cin, 64), n_ocg = cdiv(cout, 64);
-        int G = wgrad_x3_G(cin, cout);
-        if (total < G) G = total;
-        if (signs != nullptr) hipLaunchKernelGGL((wgrad_x3_kernel<8, 8, 8, 1, true>), dim3(G * n_icg * n_ocg), dim3(XW_THREADS), 0, st, tx, tg, ws, cin, cout, tiles_x, tpi, total, G, n_icg, n_ocg, signs);
-        else hipLaunchKernelGGL((wgrad_x3_kernel<8, 8, 8, 1>), dim3(G * n_icg * n_ocg), dim3(XW_THREADS), 0, st, tx, tg, ws, cin, cout, tiles_x, tpi, total, G, n_icg, n_ocg, signs);
-        if (int rc = check_launch("wgrad_x3 1x1")) return rc;
-        return wgrad_reduce_launch(wgrad_x3_reduce{dw, db, cin, cout, n_icg, n_ocg, 1}, ws, 3 * G, accumulate, st);   // (three k-split partials per block)
+// launches what the route says (x3_wgrad_route), then the reduce of its red_G partials
+int wgrad_x3(const X3WgradRoute& r, const TV& tx, const TV& tg, float* dw, float* db, int cin, int cout, int accumulate, float* ws, hipStream_t st, unsigned* signs) {
+    if (r.kernel == X3WgradRoute::THIN) {
+#define X3_THIN(...) hipLaunchKernelGGL((wgrad_x3_thin_kernel<__VA_ARGS__>), dim3(r.G), dim3(XT_THREADS), 0, st, tx, tg, ws, r.tiles_x, r.tpi, r.total, signs)
+        if (r.nxc == 2) { if (signs != nullptr) X3_THIN(2, true); else X3_THIN(2); }
+        else if (r.nxc == 4) { if (signs != nullptr) X3_THIN(4, true); else X3_THIN(4); }
+        else { if (signs != nullptr) X3_THIN(6, true); else X3_THIN(6); }
+#undef X3_THIN
+        if (int rc = check_launch("wgrad_x3 thin")) return rc;
+        return wgrad_reduce_launch(wgrad_x3_thin_reduce{dw, db, cin, cout}, ws, r.red_G, accumulate, st);
     }
-    const bool thin = cin <= 48 && cout <= 16;
-    if (thin) {
-        const int tiles_x = cdiv(tx.w, XT_TW), tiles_y = cdiv(tx.h, XT_TH);
-        const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-        int G = x3_num_cus() * (cin <= 16 ? 5 : (cin <= 32 ? 4 : 3));   // blocks per CU: what the registers (92 / 128 / 168) and the LDS (20 / 32 / 44 KB) allow
-        if (total < G) G = total;
-        if ((size_t)G * XT_PER * sizeof(float) <= wgrad_x3_workspace(cin, cout, 3)) {
-#define XT_LAUNCH(...) hipLaunchKernelGGL((wgrad_x3_thin_kernel<__VA_ARGS__>), dim3(G), dim3(XT_THREADS), 0, st, tx, tg, ws, tiles_x, tpi, total, signs)
-            if (cin <= 16) { if (signs != nullptr) XT_LAUNCH(2, true); else XT_LAUNCH(2); }
-            else if (cin <= 32) { if (signs != nullptr) XT_LAUNCH(4, true); else XT_LAUNCH(4); }
-            else { if (signs != nullptr) XT_LAUNCH(6, true); else XT_LAUNCH(6); }
-#undef XT_LAUNCH
-            if (int rc = check_launch("wgrad_x3 thin")) return rc;
-            return wgrad_reduce_launch(wgrad_x3_thin_reduce{dw, db, cin, cout}, ws, G, accumulate, st);
-        }
-    }
-    const int th = thin ? 16 : 8;
-    const int tiles_x = cdiv(tx.w, XW_TW), tiles_y = cdiv(tx.h, th);
-    const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-    const int n_icg = cdiv(cin, 64), n_ocg = cdiv(cout, 64);
-    int G = wgrad_x3_G(cin, cout);
-    if (total < G) G = total;
     static int abl = -1;
     if (abl < 0) abl = ablate_env("x3");
-    const int tx_abl = tiles_x | (abl << 16);
-#define XW_LAUNCH(...) hipLaunchKernelGGL((wgrad_x3_kernel<__VA_ARGS__>), dim3(G * n_icg * n_ocg), dim3(XW_THREADS), 0, st, tx, tg, ws, cin, cout, tx_abl, tpi, total, G, n_icg, n_ocg, signs)
-    if (thin) { if (signs != nullptr) XW_LAUNCH(16, 6, 2, 3, true); else XW_LAUNCH(16, 6, 2, 3); }
-    else { if (signs != nullptr) XW_LAUNCH(8, 8, 8, 3, true); else XW_LAUNCH(8, 8, 8, 3); }
-#undef XW_LAUNCH
-    if (int rc = check_launch("wgrad_x3")) return rc;
-    return wgrad_reduce_launch(wgrad_x3_reduce{dw, db, cin, cout, n_icg, n_ocg, 9}, ws, G, accumulate, st);
+    const bool k1 = r.kernel == X3WgradRoute::K1;
+    const int tx_abl = k1 ? r.tiles_x : r.tiles_x | (abl << 16);
+#define X3_WIDE(...) hipLaunchKernelGGL((wgrad_x3_kernel<__VA_ARGS__>), dim3(r.G * r.n_icg * r.n_ocg), dim3(XW_THREADS), 0, st, tx, tg, ws, cin, cout, tx_abl, r.tpi, r.total, r.G, r.n_icg, r.n_ocg, signs)
+    if (k1) { if (signs != nullptr) X3_WIDE(8, 8, 8, 1, true); else X3_WIDE(8, 8, 8, 1); }
+    else if (r.kernel == X3WgradRoute::THIN16) { if (signs != nullptr) X3_WIDE(16, 6, 2, 3, true); else X3_WIDE(16, 6, 2, 3); }
+    else { if (signs != nullptr) X3_WIDE(8, 8, 8, 3, true); else X3_WIDE(8, 8, 8, 3); }
+#undef X3_WIDE
+    if (int rc = check_launch(k1 ? "wgrad_x3 1x1" : "wgrad_x3")) return rc;
+    return wgrad_reduce_launch(wgrad_x3_reduce{dw, db, cin, cout, r.n_icg, r.n_ocg, k1 ? 1 : 9}, ws, r.red_G, accumulate, st);
 }
-
 
 // dW / db of the three DenseBlock convs of one encoder: tx = [x0 | x1 | x2] (>= 6 channel blocks), tg = [g1 | g2 | g3] (6 blocks)
 bool wgrad_x3_dense_supported(const TV& tx, const TV& tg) {
     return x3_enabled() && x3_grad_ok(tg) && tx.halo == 0 && tx.h >= 2 && tx.w >= 2 && x3_small(tx) && x3_small(tg) && tx.cb >= 6 && tg.cb == 6;
 }
-size_t wgrad_x3_dense_workspace() { return (size_t)2 * 256 * XD_PER * sizeof(float); }
+size_t wgrad_x3_dense_workspace() { return (size_t)XD_MAXG * XD_PER * sizeof(float); }
 int wgrad_x3_dense(const TV& tx, const TV& tg, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, int accumulate, float* ws,
                    hipStream_t st) {
     const int tiles_x = cdiv(tx.w, XT_TW), tiles_y = cdiv(tx.h, XT_TH);
     const int tpi = tiles_x * tiles_y, total = tpi * tx.n;
-    int G = x3_num_cus() * 2;
-    if (G > 512) G = 512;
-    if (total < G) G = total;
+    const int G = x3_dense_G(total, cached_num_cus());
     hipLaunchKernelGGL(wgrad_x3_dense_kernel, dim3(G), dim3(XT_THREADS), 0, st, tx, tg, ws, tiles_x, tpi, total);
     if (int rc = check_launch("wgrad_x3 dense")) return rc;
     return wgrad_reduce_launch(wgrad_x3_dense_reduce{{dw1, dw2, dw3}, {db1, db2, db3}}, ws, G, accumulate, st);

@@ -104,11 +104,23 @@ def expected_kernel(op, dtype, cin, cout, n, h, w, gy_folded=True, fold=False, m
     return r.name if r is not None else "none"
 
 
+# The fp32 split-operand family (csrc/conv_x3.hip), one name per code object.  Forward kernels exist per operand format (h16: two scaled fp16
+# pieces, b3 / b2: three / two bf16 pieces -- mmif_set_x3_forward_pieces(16 | 3 | 2)); the input gradient always reads two bf16 pieces.
+X3_FORMATS = (16, 3, 2)
+X3_LABELS = (["x3<%d,mb%d,%s>" % (k, mb, f) for k in (1, 3) for mb in (2, 1) for f in ("h16", "b3", "b2") if (k, mb, f) != (3, 1, "b3")]
+             + ["x3<3,mb1,b3,rj4>"] + ["x3<3,mb1,%s,nw4%s>" % (f, m) for f in ("h16", "b2") for m in ("", ",m16")]
+             + ["x3_dgrad<1,mb2>", "x3_dgrad<1,mb1>", "x3_dgrad<3,mb2>", "x3_dgrad<3,mb1>", "x3_dgrad<3,mb1,nw4>", "x3_dgrad<3,mb1,nw4,m16>"]
+             + ["x3_wgrad<1>", "x3_wgrad<3>"] + ["x3_wgrad_thin<%d>" % c for c in (2, 4, 6)])
+# No legal call reaches it on a part with <= 256 compute units (every gfx950 part): the route takes wgrad_x3_kernel<16,6,2,3> only where the
+# thin kernel's partials (up to 5 blocks per CU x 6976 floats) outgrow the workspace of 256 partials of 36928 floats, i.e. past 270
+# compute units.  tests/test_conv_oracle_cpu.py proves both halves on a grid of shapes.
+UNREACHABLE = {"x3_wgrad_thin16"}
+
 # every kernel name the sweep must reach (tests/test_conv_oracle_cpu.py fails on an unreached one)
 REQUIRED_LABELS = (["mfma<3,%d>" % m for m in (1, 2, 3, 4)] + ["mfma<1,%d>" % m for m in (2, 3, 4)] + ["conv1x1_stream"]
                    + ["conv_dma<L0,org0>", "conv_dma<L0,org1>", "conv_dma<L1,org0>", "conv_dma<L1,org1>", "conv_dma<L2,org1>", "conv_dma<L0,org1,dup>"]
                    + ["thin_async<1>", "thin_async<2>", "thin_async<3>", "thin_wide", "wgrad_dma", "wgrad_taprow"]
-                   + ["wgrad_mfma<3,%d>" % m for m in (1, 2, 4)] + ["wgrad_mfma<1,4,2,%d>" % i for i in (1, 2, 4)] + ["bwd_pair", "x3", "valu"])
+                   + ["wgrad_mfma<3,%d>" % m for m in (1, 2, 4)] + ["wgrad_mfma<1,4,2,%d>" % i for i in (1, 2, 4)] + ["bwd_pair", "valu"] + X3_LABELS)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -116,7 +128,7 @@ REQUIRED_LABELS = (["mfma<3,%d>" % m for m in (1, 2, 3, 4)] + ["mfma<1,%d>" % m 
 # ------------------------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class Case:
-    label: str            # the kernel the case is meant to reach at num_cus = 256
+    label: str            # the kernel the case is meant to reach at num_cus = 256 (x3 forward: in the default operand format, h16)
     op: str               # fwd | dgrad | dgrad_onto | wgrad | bwd_pair | bwd_wide | dgrad_dup
     cin: int
     cout: int
@@ -140,7 +152,8 @@ class Case:
 
     @property
     def id(self):
-        s = f"{self.label}-{self.op}{'F' if self.fold else ''}-{self.dtype}-{self.cin}to{self.cout}k{self.k}-{self.n}x{self.h}x{self.w}"
+        head = "x3" if self.impl == "x3" else self.label      # (the x3 ids name the family: they predate the per-kernel labels)
+        s = f"{head}-{self.op}{'F' if self.fold else ''}-{self.dtype}-{self.cin}to{self.cout}k{self.k}-{self.n}x{self.h}x{self.w}"
         if not self.gy_folded:
             s += "-gyraw"
         if self.gy_halo == 0:
@@ -163,6 +176,19 @@ class Case:
     def expected(self, num_cus=256, mask_bits=None, accum_bits=None):
         r = self.route(num_cus, mask_bits, accum_bits)
         return r.name if r is not None else "none"
+
+    def x3_forward_labels(self, num_cus=256):
+        """{operand format: kernel} of an x3 forward case: the sweep runs it in each of the three (the process mode is put back afterwards)"""
+        from mmif._lib import lib
+        prev = lib.mmif_get_x3_forward_pieces()
+        try:
+            out = {}
+            for pieces in X3_FORMATS:
+                lib.mmif_set_x3_forward_pieces(pieces)
+                out[pieces] = self.expected(num_cus)
+            return out
+        finally:
+            lib.mmif_set_x3_forward_pieces(prev)
 
 
 NO_DMA = (("conv_dma", 0),)
@@ -237,15 +263,18 @@ def _cases():
     for n, h, w in [(2, 33, 40), (1, 4, 4), (1, 64, 48)]:
         cs.append(Case("conv_dma<L0,org1,dup>", "dgrad_dup", 64, 64, n, h, w, fold=True))
     # ---- fp32 tensors: the split-operand (x3) and the fp32 FMA (valu) kernels; one map per tile-edge class
+    x3 = {(16, 16): ("x3<3,mb1,h16,nw4,m16>", "x3_dgrad<3,mb1,nw4,m16>", "x3_wgrad_thin<2>"), (48, 16): ("x3<3,mb1,h16,nw4,m16>", "x3_dgrad<3,mb2>", "x3_wgrad_thin<6>"),
+          (72, 64): ("x3<3,mb2,h16>", "x3_dgrad<3,mb2>", "x3_wgrad<3>"), (13, 21): ("x3<3,mb1,h16,nw4>", "x3_dgrad<3,mb1,nw4,m16>", "x3_wgrad<3>")}
     for impl in ("x3", "valu"):
         for cin, cout in [(16, 16), (48, 16), (72, 64), (13, 21)]:
+            lf, ld, lw = x3[cin, cout] if impl == "x3" else (impl,) * 3
             for n, h, w in [(2, 33, 40), (1, 16, 16), (2, 17, 17), (2, 2, 9), (1, 3, 3), (2, 5, 7)]:
-                cs.append(Case(impl, "fwd", cin, cout, n, h, w, dtype="f32", impl=impl))
-                cs.append(Case(impl, "dgrad", cin, cout, n, h, w, dtype="f32", impl=impl, fold=True, bits=FEW_BITS))
-                cs.append(Case(impl, "wgrad", cin, cout, n, h, w, dtype="f32", impl=impl, accumulate=(0, 1)))
-            cs.append(Case(impl, "dgrad", cin, cout, 2, 33, 40, dtype="f32", impl=impl, fold=False, bits=FEW_BITS))
+                cs.append(Case(lf, "fwd", cin, cout, n, h, w, dtype="f32", impl=impl))
+                cs.append(Case(ld, "dgrad", cin, cout, n, h, w, dtype="f32", impl=impl, fold=True, bits=FEW_BITS))
+                cs.append(Case(lw, "wgrad", cin, cout, n, h, w, dtype="f32", impl=impl, accumulate=(0, 1)))
+            cs.append(Case(ld, "dgrad", cin, cout, 2, 33, 40, dtype="f32", impl=impl, fold=False, bits=FEW_BITS))
     for cin, cout in [(72, 64), (13, 21)]:      # x3 dgrad masked by the sign map its weight gradient leaves
-        cs.append(Case("x3", "bwd_wide", cin, cout, 2, 33, 40, dtype="f32", impl="x3", bits=((ALL, 0), (M5A, 0)), accumulate=(0, 1)))
+        cs.append(Case(x3[cin, cout][1], "bwd_wide", cin, cout, 2, 33, 40, dtype="f32", impl="x3", bits=((ALL, 0), (M5A, 0)), accumulate=(0, 1)))
     # ---- 1x1 layers
     for cin, cout in [(8, 64), (88, 64), (24, 40)]:
         for n, h, w in [(3, 33, 40), (1, 16, 16), (2, 5, 7)]:
@@ -255,6 +284,22 @@ def _cases():
             cs.append(Case(f"mfma<1,{pick_mf(cin)}>", "dgrad", cin, cout, n, h, w, k=1, gy_halo=0, gx_halo=0, bits=((M5A, M33), (0, ALL))))
     for cin, cout in [(40, 24), (24, 40), (88, 64)]:
         cs.append(Case(f"mfma<1,{pick_mf(cout)}>", "fwd", cin, cout, 3, 33, 40, k=1, switches=(("conv1x1_stream", 0),)))
+    # ---- the x3 kernels the four fp32 layers above do not reach (last: the cases before them keep their places), on the tile-edge maps (1x3x3: the folded dgrad below h = 4 leaves the fold to the
+    # stand-alone kernel): eight-wave blocks at <= 32 outputs (> 64 inputs), the four-wave dgrad at 17..32 outputs, the 17..32-input thin
+    # weight gradient, and every 1x1 kernel
+    f32 = dict(dtype="f32", impl="x3")
+    for n, h, w in [(2, 33, 40), (2, 5, 7)]:
+        cs.append(Case("x3<3,mb1,h16>", "fwd", 72, 24, n, h, w, **f32))
+        cs.append(Case("x3_wgrad_thin<4>", "wgrad", 24, 12, n, h, w, accumulate=(0, 1), **f32))
+    for n, h, w in [(2, 33, 40), (2, 5, 7), (1, 3, 3)]:
+        cs.append(Case("x3_dgrad<3,mb1>", "dgrad", 24, 72, n, h, w, fold=True, bits=FEW_BITS, **f32))
+        cs.append(Case("x3_dgrad<3,mb1,nw4>", "dgrad", 24, 40, n, h, w, fold=True, bits=FEW_BITS, **f32))
+    for n, h, w in [(2, 33, 40), (2, 5, 7)]:
+        for cin, cout in [(24, 40), (88, 64)]:
+            cs.append(Case("x3<1,mb2,h16>", "fwd", cin, cout, n, h, w, k=1, **f32))
+            cs.append(Case(f"x3_dgrad<1,mb{2 if cin > 32 else 1}>", "dgrad", cin, cout, n, h, w, k=1, gy_halo=0, gx_halo=0, bits=FEW_BITS, **f32))
+            cs.append(Case("x3_wgrad<1>", "wgrad", cin, cout, n, h, w, k=1, accumulate=(0, 1), **f32))
+        cs.append(Case("x3<1,mb1,h16>", "fwd", 40, 24, n, h, w, k=1, **f32))
     return cs
 
 

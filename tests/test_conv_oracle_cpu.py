@@ -109,13 +109,21 @@ def test_definitions_equal_golden_f3(case):
 
 
 def test_every_case_reaches_its_kernel_and_every_kernel_is_reached():
-    """at 256 compute units the library's dispatch gives each case's label for every bit pair it runs; every required name has a case"""
+    """at 256 compute units the library's dispatch gives each case's label for every bit pair it runs; every required name has a case.  An x3
+    forward case runs in the three operand formats (tests/test_gpu_conv_sweep.py): it reaches the kernel of each"""
     wrong = [(c.id, m, a, c.expected(256, m, a)) for c in CASES for m, a in c.bits if c.expected(256, m, a) != c.label]
     assert not wrong, wrong[:10]
     reached = {c.label for c in CASES}
+    for c in CASES:
+        if c.impl == "x3" and c.op == "fwd":
+            by_format = c.x3_forward_labels()
+            assert by_format[16] == c.label and len(set(by_format.values())) == 3, (c.id, by_format)
+            reached |= set(by_format.values())
     missing = [l for l in CC.REQUIRED_LABELS if l not in reached]
     print("unreached kernels:", missing)
     assert not missing, missing
+    assert len(set(CC.REQUIRED_LABELS)) == len(CC.REQUIRED_LABELS) and not reached & CC.UNREACHABLE
+    assert all(len(l) < 32 for l in CC.REQUIRED_LABELS + sorted(CC.UNREACHABLE)), "mmif_route.name is char[32]"
 
 
 def test_tile_thresholds_of_the_asynchronous_kernel():
@@ -181,3 +189,131 @@ def test_case_is_not_vacuous(c):
             if (a >> blk) & 1:
                 r = np.abs(o.old[inner][:, ch]).mean() / np.abs(new[inner][:, ch]).mean()
                 assert 0.1 <= r <= 10, f"{c.id}: block {blk}: |old| / |new| = {r}"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the fp32 split-operand (x3) routes on a grid of geometries: what the launches take from csrc/conv_route.hpp, asked through
+# mmif_conv2d_route and mmif_conv2d_wgrad_workspace
+# ------------------------------------------------------------------------------------------------------------------------------
+X3_CH = (1, 8, 13, 16, 17, 32, 33, 48, 49, 64, 65, 72, 128, 136)
+X3_MAPS = [(2, 33, 40), (1, 16, 16), (2, 17, 17), (2, 2, 9), (1, 3, 3), (2, 5, 7), (1, 512, 512)]
+X3_CUS = (8, 64, 256, 304)
+XT_PER = 9 * 768 + 64                  # floats of one wgrad_x3_thin_kernel partial (csrc/wgrad_reduce.hpp)
+
+
+def _xw_per(cin, cout, k):
+    """floats of one wgrad_x3_kernel tile group: a [64 x 64 x taps | 64] partial per 64 x 64 channel pair (wgrad_x3_reduce::per)"""
+    return CC.cdiv(cin, 64) * CC.cdiv(cout, 64) * (64 * 64 * k * k + 64)
+
+
+def _x3_formats(fn):
+    from mmif._lib import lib
+    prev = lib.mmif_get_x3_forward_pieces()
+    try:
+        for pieces in CC.X3_FORMATS:
+            lib.mmif_set_x3_forward_pieces(pieces)
+            fn(pieces)
+    finally:
+        lib.mmif_set_x3_forward_pieces(prev)
+
+
+def test_x3_forward_and_dgrad_routes_on_a_grid():
+    """every legal call is taken; the name says the operation, the kernel size, the operand format and the M-block width asked for, and the
+    tile geometry it names (32 columns x 16 rows; nw4: 8 rows, three blocks per compute unit; rj4: 32 rows) is the one the grid is sized by:
+    1 <= G = min(tiles, blocks per CU x compute units); org = 1 exactly for the folded 3x3 call at h, w >= 4 off the m16 kernel"""
+    seen = {}
+
+    def check(pieces):
+        fmt = {16: "h16", 3: "b3", 2: "b2"}[pieces]
+        for k in (1, 3):
+            for (n, h, w) in X3_MAPS:
+                for cin in X3_CH:
+                    for cout in X3_CH:
+                        for ncu in X3_CUS:
+                            calls = [("fwd", False, cout)] + ([("dgrad", f, cin) for f in (False, True)] if pieces == 16 else [])
+                            for op, fold, n_out in calls:
+                                r = CC.route(op, "f32", cin, cout, n, h, w, fold=fold, k=k, impl="x3", num_cus=ncu)
+                                what = (op, fold, k, cin, cout, n, h, w, ncu, r)
+                                assert r is not None and r.name in CC.X3_LABELS, what
+                                head, _, args = r.name[:-1].partition("<")
+                                args = args.split(",")
+                                assert head == ("x3" if op == "fwd" else "x3_dgrad") and args[0] == str(k) and args[1] == f"mb{2 if n_out > 32 else 1}", what
+                                assert (args[2] == fmt) if op == "fwd" else not {"h16", "b3", "b2"} & set(args), what
+                                rows, per_cu = (8, 3) if "nw4" in args else ((32, 1) if "rj4" in args else (16, 1))
+                                halo = 1 if op == "dgrad" else 0          # (the tiles cover gx's stored extent; these gx have a halo of 1)
+                                assert r.org == (1 if (fold and k == 3 and h >= 4 and w >= 4 and "m16" not in args) else 0), what
+                                ext = 2 * (halo - r.org)
+                                assert r.tiles == n * CC.cdiv(h + ext, rows) * CC.cdiv(w + ext, 32), what
+                                assert 1 <= r.G == min(r.tiles, per_cu * ncu) and r.slices == 0, what
+                                seen.setdefault(r.name, set()).add((op, k, n_out > 32, pieces if op == "fwd" else 0))
+    _x3_formats(check)
+    assert all(len(v) == 1 for v in seen.values()), "one name, one (operation, kernel size, M-block width, format)"
+    assert set(seen) == {l for l in CC.X3_LABELS if "wgrad" not in l}, "the grid reaches every forward / input-gradient kernel and no other name"
+
+
+def test_x3_weight_gradient_routes_fit_the_workspace_on_a_grid():
+    """1 <= G <= tiles per launched tile group (the 1x1 kernel leaves three k-split partials per block: the reduce's G is three times that), and the
+    partials the reduce sums fit the workspace mmif_conv2d_wgrad_workspace answers for the layer, whatever the compute units -- the
+    property the thin launcher used to guard at run time.  The <16,6,2,3> fallback is taken by no call up to 256 compute units; it is
+    what keeps the property at 304, where five thin blocks per CU would outgrow the workspace."""
+    from mmif import tensor as T
+    seen = {}
+    for k in (1, 3):
+        for cin in X3_CH:
+            for cout in X3_CH:
+                ws = T.wgrad_workspace_bytes(cin, cout, k)
+                for (n, h, w) in X3_MAPS:
+                    for ncu in X3_CUS:
+                        r = CC.route("wgrad", "f32", cin, cout, n, h, w, k=k, impl="x3", num_cus=ncu)
+                        what = (k, cin, cout, n, h, w, ncu, r)
+                        assert r is not None and r.name in set(CC.X3_LABELS) | CC.UNREACHABLE, what
+                        thin = r.name.startswith("x3_wgrad_thin<")
+                        assert thin == (k == 3 and cin <= 48 and cout <= 16 and r.name != "x3_wgrad_thin16"), what
+                        th = 16 if r.name == "x3_wgrad_thin16" else 8
+                        assert r.tiles == n * CC.cdiv(h, th) * CC.cdiv(w, 16), what
+                        split = 3 if k == 1 else 1
+                        assert r.G % split == 0 and 1 <= r.G // split <= r.tiles, what
+                        assert r.slices == (16 if (thin or r.G > 64) else 4), what
+                        assert r.G * (XT_PER if thin else _xw_per(cin, cout, k)) * 4 <= ws, what
+                        assert r.name != "x3_wgrad_thin16" or ncu > 256, what
+                        seen.setdefault(r.name, set()).add((k, 2 if cin <= 16 else (4 if cin <= 32 else 6)) if thin else (k,))
+    assert all(len(v) == 1 for v in seen.values()), "one name, one kernel"
+    assert set(seen) == {l for l in CC.X3_LABELS if "wgrad" in l} | CC.UNREACHABLE
+    assert CC.expected_kernel("wgrad", "f32", 16, 16, 1, 512, 512, impl="x3", num_cus=304) == "x3_wgrad_thin16"      # 1520 blocks x 6976 floats
+    for ncu in range(1, 257):           # ... and nowhere on a real part: every thin layer class, more tiles than any grid
+        for cin in (16, 32, 48):
+            assert CC.expected_kernel("wgrad", "f32", cin, 16, 4, 512, 512, impl="x3", num_cus=ncu) == f"x3_wgrad_thin<{cin // 8}>"
+
+
+def test_x3_bwd_wide_reports_both_halves():
+    """name, tiles and org of the input-gradient half, G and slices of the weight-gradient half"""
+    for cin, cout, k in [(72, 64, 3), (13, 21, 3), (16, 16, 3), (88, 64, 1)]:
+        for (n, h, w) in X3_MAPS:
+            r = CC.route("bwd_wide", "f32", cin, cout, n, h, w, k=k, impl="x3")
+            d = CC.route("dgrad", "f32", cin, cout, n, h, w, k=k, fold=True, impl="x3")
+            g = CC.route("wgrad", "f32", cin, cout, n, h, w, k=k, impl="x3")
+            assert (r.name, r.tiles, r.org, r.G, r.slices) == (d.name, d.tiles, d.org, g.G, g.slices), (cin, cout, k, n, h, w, r, d, g)
+
+
+def test_a_refused_x3_call_has_an_empty_route():
+    from mmif import _lib as L
+
+    def ask(op, cin, cout, n, h, w, k=3, dtype=L.F32, gy_halo=1, gy_flags=L.T_FOLDED, impl=L.IMPL_X3):
+        def t(c, halo, flags=0):
+            return L.MmifTensor(None, dtype, n, h, w, halo, CC.cdiv(c, 8), 0, CC.cdiv(c, 8), flags)
+        a, b = {"fwd": (t(cin, 0), t(cout, 0)), "dgrad": (t(cout, gy_halo, gy_flags), t(cin, 1))}.get(op, (t(cin, 0), t(cout, gy_halo, gy_flags)))
+        r = L.MmifRoute()
+        r.name, r.G, r.slices, r.tiles, r.org = b"stale", 7, 7, 7, 7
+        taken = L.lib.mmif_conv2d_route(L.ROUTE_OPS[op], a, b, cin, cout, k, 0, 0, 0, impl, 256, r)
+        return taken, (r.name, r.G, r.slices, r.tiles, r.org)
+
+    assert ask("fwd", 16, 16, 1, 16, 16)[0] == 1 and ask("dgrad", 16, 16, 1, 16, 16)[0] == 1 and ask("wgrad", 16, 16, 1, 16, 16)[0] == 1
+    assert ask("fwd", 16, 16, 1, 4096, 4095)[0] == 1, "the last plane eight of which 32-bit byte offsets address"
+    refused = [ask("fwd", 16, 16, 1, 16, 16, dtype=L.BF16),                     # the x3 kernels take fp32 tensors
+               ask("fwd", 16, 16, 1, 1, 16), ask("wgrad", 16, 16, 1, 16, 1),    # reflect padding needs h, w >= 2
+               ask("fwd", 16, 520, 1, 16, 16), ask("dgrad", 520, 16, 1, 16, 16),        # mask / accumulate bits address 64 channel blocks
+               ask("bwd_wide", 520, 16, 1, 16, 16),
+               ask("dgrad", 16, 16, 1, 16, 16, gy_flags=0), ask("wgrad", 16, 16, 1, 16, 16, gy_flags=0),   # a padded-domain gradient
+               ask("bwd_wide", 16, 16, 1, 16, 16, gy_flags=0),
+               ask("fwd", 16, 16, 1, 4096, 4096), ask("wgrad", 16, 16, 1, 4096, 4096)]
+    assert all(r == (0, (b"", 0, 0, 0, 0)) for r in refused), refused

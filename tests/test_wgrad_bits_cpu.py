@@ -64,7 +64,7 @@ def test_conv_wgrad_cases_take_the_route_their_flavour_names():
     """the library's dispatch (conv_cases.expected_kernel asks mmif_conv2d_route) for every conv_wgrad case of the table, and the slice
     count of its reduce"""
     import conv_cases as CC
-    want = {"wgrad_dma_reduce": "wgrad_dma", "taprow_wgrad_reduce": "wgrad_taprow", "wgrad_x3_reduce": "x3", "wgrad_x3_thin_reduce": "x3"}
+    want = {"wgrad_dma_reduce": "wgrad_dma", "taprow_wgrad_reduce": "wgrad_taprow", "wgrad_x3_thin_reduce": "x3_wgrad_thin<6>"}
     routes = set()
     for c in B.CASES:
         if c.op != "wgrad":
@@ -75,11 +75,11 @@ def test_conv_wgrad_cases_take_the_route_their_flavour_names():
             ks, mfw, icf = c.reduces[0][0].split("<")[1].split(">")[0].split(",")
             assert route == (f"wgrad_mfma<3,{mfw}>" if ks == "3" else f"wgrad_mfma<1,{mfw},2,{icf}>"), (c.id, route)
         else:
-            assert route == want[flavour], (c.id, route)
-        if c.dtype == "bf16":
-            r = CC.route("wgrad", c.dtype, c.cin, c.cout, c.n, c.h, c.w, k=c.k, impl="mfma", num_cus=B.NUM_CUS)
-            assert (r.G, r.slices) == c.reduces[0][1:], (c.id, r)
+            assert route == (f"x3_wgrad<{c.k}>" if flavour == "wgrad_x3_reduce" else want[flavour]), (c.id, route)
+        r = CC.route("wgrad", c.dtype, c.cin, c.cout, c.n, c.h, c.w, k=c.k, impl="x3" if c.dtype == "f32" else "mfma", num_cus=B.NUM_CUS)
+        assert (r.G, r.slices) == c.reduces[0][1:], (c.id, r)
         if flavour == "wgrad_x3_thin_reduce":
             assert c.cin <= 48 and c.cout <= 16 and c.k == 3, c.id
         routes.add(route)
-    assert {"wgrad_dma", "wgrad_taprow", "wgrad_mfma<3,1>", "wgrad_mfma<3,4>", "wgrad_mfma<1,4,2,4>", "wgrad_mfma<1,4,2,2>", "x3"} <= routes
+    assert {"wgrad_dma", "wgrad_taprow", "wgrad_mfma<3,1>", "wgrad_mfma<3,4>", "wgrad_mfma<1,4,2,4>", "wgrad_mfma<1,4,2,2>", "x3_wgrad<3>", "x3_wgrad<1>",
+            "x3_wgrad_thin<6>"} <= routes

@@ -12,10 +12,10 @@ tail):
     main+tail   G > 4 SL and G mod 4 SL != 0    main loop, then a tail of another length in some slices
 The flavours whose SL follows G (wgrad_dma, wgrad_x3: SL = 16 if G > 64 else 4) cannot reach `tail` at SL 16 (G > 64 > 48).
 
-The ConvLayer calls' G comes from the library (mmif_conv2d_route at 256 compute units: the route the launch itself takes); the x3, image
-and encoder kernels' G is not exported and is derived below from their launchers' formulas (for 256 compute units where the formula has
-them; the shapes here keep G = the tile count, below every such cap).  tests/test_wgrad_bits_cpu.py checks both.  Shapes are the smallest that
-reach the regime: 16 x 16-tile producers run 2 x 33 x 40 (18 tiles), 1 x 33 x 40 (9) and 3 x 80 x 96 (90).
+The ConvLayer calls' G, bf16 and fp32 (x3), comes from the library (mmif_conv2d_route at 256 compute units: the route the launch itself
+takes); the image, encoder and dense x3 kernels' G is not exported and is derived below from their launchers' formulas (for 256 compute
+units where the formula has them; the shapes here keep G = the tile count, below every such cap).  tests/test_wgrad_bits_cpu.py checks both.
+Shapes are the smallest that reach the regime: 16 x 16-tile producers run 2 x 33 x 40 (18 tiles), 1 x 33 x 40 (9) and 3 x 80 x 96 (90).
 """
 from __future__ import annotations
 
@@ -46,9 +46,9 @@ def sl_by_G(G):
     return 16 if G > 64 else 4
 
 
-def _G(op, kernel, cin, cout, k, n, h, w):
+def _G(op, kernel, cin, cout, k, n, h, w, dtype="bf16"):
     """G of the library's route for the call, which must be the kernel the caller means"""
-    r = CC.route(op, "bf16", cin, cout, n, h, w, k=k, impl="mfma", num_cus=NUM_CUS)
+    r = CC.route(op, dtype, cin, cout, n, h, w, k=k, impl="mfma" if dtype == "bf16" else "x3", num_cus=NUM_CUS)
     assert r is not None and r.name.startswith(kernel), (op, kernel, cin, cout, k, n, h, w, r)
     return r.G
 
@@ -71,16 +71,16 @@ def G_pair(cin, n, h, w):
 
 def G_x3(cin, cout, k, n, h, w):
     """the reduce's G: the 1x1 kernel leaves three k-split partials per block"""
-    G = NUM_CUS // (cdiv(cin, 64) * cdiv(cout, 64))
-    G = max(G & ~7 if G >= 8 else G, 1)
-    return min(G, tiles(n, h, w, 8, 16)) * (3 if k == 1 else 1)
+    return _G("wgrad", f"x3_wgrad<{k}>", cin, cout, k, n, h, w, "f32")
 
 
-def G_x3_thin(cin, n, h, w):
-    return min(NUM_CUS * (5 if cin <= 16 else (4 if cin <= 32 else 3)), tiles(n, h, w, 8, 16))
+def G_x3_thin(cin, n, h, w, cout=16):
+    return _G("wgrad", "x3_wgrad_thin<", cin, cout, 3, n, h, w, "f32")
 
 
 def G_x3_dense(n, h, w):
+    """mmif_dense_encoder_wgrad on fp32 tensors is no ConvLayer call: mmif_conv2d_route has no op for it (x3_dense_G, csrc/conv_route.hpp:
+    two blocks per compute unit, at most 512, at most one per 8 x 16 tile)"""
     return min(min(2 * NUM_CUS, 512), tiles(n, h, w, 8, 16))
 
 
